@@ -7,7 +7,13 @@ no data-path collective) -> strong scaling. A step = GaussianRenderer.render (co
 in-kernel) of the rank's scenes + autograd backward to dL/dgaussians for fixed seeded upstream gradients of image
 and alpha (LGM's loss inputs, core/models.py:141-153). value = all pixels of the pool / max-over-ranks time.
 
-Secondary objects on the same line:
+A plain run does that and no more: set-up, W warmup steps, K timed steps, one JSON line (metric, value, unit,
+ms_per_step, ... and the timed loop's per-step stamps). --dump-outputs DIR also writes what the last timed step
+returned (image, alpha, depth, dL/dgaussians; float32 .npy, large arrays as a fixed seeded sample: dump_outputs),
+the inputs being seeded and so identical from run to run. Everything below needs --full.
+
+With --full the line also carries the pool's per-kernel times (a second, profiled pass), step spread, deterministic
+mode and rooflines, and these secondary objects:
   * "cfg3_view_sharded": ONE cfg3 scene (seed 1) whose 6 views are split over the G ranks, plus the RCCL SUM
     all-reduce of dL/dgaussians [1,N,14] (SURVEY §8(e)); at G = 1 this is exactly BASELINE config 3;
   * "cfg2": 50k Gaussians x 1 view x 256^2 forward only (BASELINE config 2), rank 0;
@@ -18,7 +24,7 @@ Secondary objects on the same line:
   * "roofline": the dominant kernel priced with SURVEY §8(d)'s algorithmic bytes over its HIP-event time;
   * "cpu_baseline": the CPU oracle port on all host cores (rank 0, N = 1).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 With --gpus N > 1 and no torchrun environment, bench.py spawns the N ranks itself (before any GPU call).
 """
 from __future__ import annotations
@@ -513,6 +519,24 @@ def cfg5_bench(dev, info, steps):
     return res
 
 
+DUMP_MAX_ELEMS, DUMP_SEED = 4_000_000, 0  # per array: 4 arrays x 16 MB stay under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step returned to its caller (rank 0's scenes), one float32 .npy per
+    array. An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of its flattened elements
+    (DUMP_MAX_ELEMS sorted indices drawn without replacement by numpy's default_rng(DUMP_SEED): the same elements in
+    every run and every build, so two dumps compare element for element)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        flat = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        if flat.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, DUMP_MAX_ELEMS, replace=False))
+            a = flat[idx]
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def run(args):
     import torch
 
@@ -549,19 +573,57 @@ def run(args):
     cpd = cp[None].expand(B, -1, -1).contiguous().to(dev)
     bgd = bg.to(dev)
     d_imgd, d_alphad = d_img[s0:s1].contiguous().to(dev), d_alpha[s0:s1].contiguous().to(dev)
-    K_binned, K = count_pairs(g.detach(), cvd, cvpd, tan, tan, RES, RES) if B else (0, 0)
+    keep = [bool(args.dump_outputs) and rank == 0]  # --dump-outputs: hold on to each step's results (the last remain)
+    last = {}
 
     def step():
         if B == 0:
             return
         out = renderer.render(g, cvd, cvpd, cpd, bg_color=bgd)
         torch.autograd.backward([out["image"], out["alpha"]], [d_imgd, d_alphad])
+        if keep[0]:
+            last.update(image=out["image"].detach(), alpha=out["alpha"].detach(), depth=out["depth"].detach(),
+                        d_gaussians=g.grad)
         g.grad = None
 
     D.warm_up(step, args.warmup, torch.cuda.synchronize, info, dev)  # (>= 50 ms: the clocks' ramp, dist.warm_up)
-    # timed steps with nothing attached; per-kernel HIP-event times from a second, untimed pass of the same steps
+    # timed steps with nothing attached (--full: per-kernel HIP-event times from a second, untimed pass of the same
+    # steps, below)
     stamps = {}
     el = D.timed_steps(step, args.steps, info, torch.cuda.synchronize, dev, stamps=stamps)
+    if keep[0]:
+        keep[0] = False
+        dump_outputs(args.dump_outputs, {k: v.detach().cpu().numpy() for k, v in last.items()})
+        last.clear()
+    P = RES * RES
+    ms_step = 1e3 * el / args.steps
+    result = {
+        "metric": "Mpixels/s fwd+bwd Gaussian raster (256^2, 100k gauss, 6 views)",
+        "value": round(POOL_SCENES * VIEWS * P * args.steps / el / 1e6, 2),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (SURVEY.md 8(d): raw~N(0,1) through LGM activations, 6 orbit cameras r=1.5 fovy 49.1, "
+                "seeded upstream grads of image and alpha); scaling pool seed 2",
+        "config": {"workload": f"scaling pool: {POOL_SCENES} cfg3 scenes (100k Gaussians x 6 views x 256^2 each), "
+                               f"render fwd+bwd (GaussianRenderer API), sharded by scene: {B} scene(s) on rank 0",
+                   "gaussians": N_GAUSS, "views": VIEWS, "H": RES, "W": RES, "pool_scenes": POOL_SCENES,
+                   "scenes_per_gpu": B, "global_batch": POOL_SCENES,
+                   "parallelism": f"scene-sharded x{world} (no collective)"},
+        "timed_loop": stamps,
+    }
+    if not args.full:  # a plain run ends here: the headline figure alone
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        D.finalize(info)
+        return
+    K_binned, K = count_pairs(g.detach(), cvd, cvpd, tan, tan, RES, RES) if B else (0, 0)
     prof = _native.KernelProfiler()
     with prof:
         for _ in range(args.steps):
@@ -593,36 +655,11 @@ def run(args):
                "Mpixels_per_s": round(POOL_SCENES * VIEWS * RES * RES * n_det / el_det / 1e6, 2), "steps": n_det,
                "kernels": {k: {"avg_us": round(1e3 * v / n, 2), "launches": n} for k, (n, v) in kern_d.items()}}
 
-    P = RES * RES
-    pixels = POOL_SCENES * VIEWS * P * args.steps
-    value = pixels / el / 1e6
     kb = kernel_bytes(N_GAUSS, B * VIEWS, K, P, B)
     per_kernel = {k: {"avg_us": round(1e3 * ms / n, 2), "launches": n} for k, (n, ms) in kern.items()}
-    ms_step = 1e3 * el / args.steps
-    result = {
-        "metric": "Mpixels/s fwd+bwd Gaussian raster (256^2, 100k gauss, 6 views)",
-        "value": round(value, 2),
-        "unit": "Mpixels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (SURVEY.md 8(d): raw~N(0,1) through LGM activations, 6 orbit cameras r=1.5 fovy 49.1, "
-                "seeded upstream grads of image and alpha); scaling pool seed 2",
-        "config": {"workload": f"scaling pool: {POOL_SCENES} cfg3 scenes (100k Gaussians x 6 views x 256^2 each), "
-                               f"render fwd+bwd (GaussianRenderer API), sharded by scene: {B} scene(s) on rank 0",
-                   "gaussians": N_GAUSS, "views": VIEWS, "H": RES, "W": RES, "pool_scenes": POOL_SCENES,
-                   "scenes_per_gpu": B, "global_batch": POOL_SCENES, "pairs_K_reference_rank0": K,
-                   "pairs_binned_rank0": K_binned, "parallelism": f"scene-sharded x{world} (no collective)"},
-        "kernels": per_kernel,
-        "step_spread": spread,
-        "timed_loop": stamps,
-        "profiled_kernel_sum_ms_per_step": kernel_sum_ms(kern, args.steps),
-    }
+    result["config"].update(pairs_K_reference_rank0=K, pairs_binned_rank0=K_binned)
+    result.update(kernels=per_kernel, step_spread=spread,
+                  profiled_kernel_sum_ms_per_step=kernel_sum_ms(kern, args.steps))
     if det:
         det["slowdown_vs_float_atomics"] = round(det["ms_per_step"] / (1e3 * el / args.steps), 3)
         result["deterministic"] = det
@@ -733,6 +770,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also everything else this benchmark measures: per-kernel "
+                         "times, step spread, deterministic mode, rooflines, cfg2-cfg5, attention, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (image, alpha, depth, d_gaussians of rank 0's "
+                         "scenes) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-attention", action="store_true", help="skip the secondary attention measurement")
@@ -743,7 +786,12 @@ def parse(argv=None):
                     help="only the attention, MVAttention-level and cfg4 lines (attention-side A/B runs)")
     ap.add_argument("--only-pool", action="store_true",
                     help="only the headline workload (for counter profiles: no other kernel launches of other sizes)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.only_attn and not args.full:
+        ap.error("--only-attn selects among the --full measurements: pass --full with it")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():

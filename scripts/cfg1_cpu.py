@@ -17,7 +17,7 @@ own flow with lgm_amd's modules swapped in:
 fp32 throughout (infer.py:44 casts to half for CUDA; half convolutions are not a CPU path). Random init: no
 checkpoint exists offline (infer.py:32-40 warns the same way).
 
-    python scripts/cfg1_cpu.py [--reference /root/reference] [--png tests/golden/catstatue_rgba.png] [--threads N]
+    python scripts/cfg1_cpu.py --reference LGM_CHECKOUT [--png tests/golden/catstatue_rgba.png] [--threads N]
 """
 from __future__ import annotations
 
@@ -83,8 +83,6 @@ def load_views(png: str, size: int = INPUT_SIZE) -> torch.Tensor:
 
 
 def run(reference_root: str, png: str, out_dir: str, threads: int = 0, seed: int = 0) -> dict:
-    from lgm_amd import GaussianRenderer, Options
-    from lgm_amd.cameras import cameras_from_c2w, orbit_camera, projection_matrix
     from lgm_amd.head import GaussianHead
     if threads > 0:
         torch.set_num_threads(threads)
@@ -97,12 +95,22 @@ def run(reference_root: str, png: str, out_dir: str, threads: int = 0, seed: int
     t["build_s"] = time.perf_counter() - t0
     images = load_views(png)
     B, V = images.shape[:2]
-    opt = Options(input_size=INPUT_SIZE, splat_size=SPLAT_SIZE, output_size=RENDER_SIZE)
-    renderer = GaussianRenderer(opt)
     with torch.no_grad():
         t0 = time.perf_counter()
         feats = unet(images.view(B * V, 9, INPUT_SIZE, INPUT_SIZE))  # [4, 14, 128, 128]
         t["unet_s"] = time.perf_counter() - t0
+    return after_unet(feats, head, B, V, out_dir, swapped, t)
+
+
+def after_unet(feats, head, B: int, V: int, out_dir: str, swapped: int, t: dict = None) -> dict:
+    """Everything of run() that follows the UNet (no reference code involved): the Gaussian head on its output
+    `feats` [B*V, 14, 128, 128], save_ply and the one 256^2 orbit render."""
+    from lgm_amd import GaussianRenderer, Options
+    from lgm_amd.cameras import cameras_from_c2w, orbit_camera, projection_matrix
+    t = {} if t is None else t
+    opt = Options(input_size=INPUT_SIZE, splat_size=SPLAT_SIZE, output_size=RENDER_SIZE)
+    renderer = GaussianRenderer(opt)
+    with torch.no_grad():
         t0 = time.perf_counter()
         gaussians = head(feats, B, V)  # [1, 4 * 128^2, 14]
         t["head_s"] = time.perf_counter() - t0
@@ -123,7 +131,7 @@ def run(reference_root: str, png: str, out_dir: str, threads: int = 0, seed: int
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--reference", required=True, help="a checkout of the reference LGM (its core/unet.py)")
     ap.add_argument("--png", default=os.path.join(ROOT, "tests", "golden", "catstatue_rgba.png"))
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "cfg1"))
     ap.add_argument("--threads", type=int, default=0)

@@ -5,7 +5,7 @@ AB=${OUTAB:-gpurun_out/ab}; mkdir -p $AB
 for round in 1 2; do
   for lib in ${AB_LIBS:-lgm_amd/_lib/variants/lib_*.so}; do
     n=$(basename $lib .so)
-    LGM_AMD_LIB=$PWD/$lib timeout -k 10 120 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-attention --no-cfg4 --no-cfg5 > $AB/${n}_r${round}.json 2>/dev/null
+    LGM_AMD_LIB=$PWD/$lib timeout -k 10 120 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-attention --no-cfg4 --no-cfg5 > $AB/${n}_r${round}.json 2>/dev/null
     rc=$?; [ $rc -eq 0 ] || { echo "$n failed rc=$rc"; exit $rc; }
     if [ $round -eq 1 ]; then  # output hashes (variants meant to be bitwise equal must print the same)
       LGM_AMD_LIB=$PWD/$lib timeout -k 10 120 python scripts/render_hashes.py > $AB/${n}_hash.json 2>/dev/null

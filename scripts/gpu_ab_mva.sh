@@ -1,5 +1,5 @@
 #!/bin/bash
-# Attention-side A/B: bench.py --only-attn (attention level, MVAttention level, cfg4) per variant library in $AB_LIBS
+# Attention-side A/B: bench.py --full --only-attn (attention level, MVAttention level, cfg4) per variant library in $AB_LIBS
 # (default: every lgm_amd/_lib/variants/lib_*.so), 2 interleaved rounds.
 cd "$GRAFT_REPO_ROOT" || exit 1
 AB=${OUTAB:-gpurun_out/ab}; mkdir -p $AB
@@ -7,7 +7,7 @@ LIBS=${AB_LIBS:-$(ls lgm_amd/_lib/variants/lib_*.so)}
 for round in 1 2; do
   for lib in $LIBS; do
     n=$(basename $lib .so)
-    LGM_AMD_LIB=$PWD/$lib timeout -k 10 200 python bench.py --only-attn --steps 10 > $AB/mva_${n}_r${round}.json 2>/dev/null
+    LGM_AMD_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --only-attn --steps 10 > $AB/mva_${n}_r${round}.json 2>/dev/null
     rc=$?; [ $rc -eq 0 ] || { echo "$n failed rc=$rc"; exit $rc; }
     python -c "
 import json

@@ -8,14 +8,14 @@
 #   tests[=PYTEST_ARGS]  pytest -m gpu (default: the whole suite; e.g. tests=tests/test_attention.py, or
 #                        "tests=tests/test_render_gpu.py -k needle")
 #   smoke                __graft_entry__.smoke()
-#   bench[=N]            bench.py with its defaults, N times (default 1), unprofiled, as the driver runs it
-#   benchargs=ARGS       bench.py ARGS once (e.g. "benchargs=--steps 40 --only-pool")
-#   prof                 rocprofv3 --kernel-trace --stats of the default bench + per-grid split, then one rocprofv3
+#   bench[=N]            bench.py --full with its defaults, N times (default 1), unprofiled
+#   benchargs=ARGS       bench.py ARGS once (e.g. "benchargs=--full --steps 40 --only-pool")
+#   prof                 rocprofv3 --kernel-trace --stats of the default --full bench + per-grid split, then one rocprofv3
 #                        run per PMC pass of scripts/pmc_passes.txt (counters only with --kernel-trace)
 #   trace=ARGS           rocprofv3 --kernel-trace --stats of bench.py ARGS, split per grid (no counters)
 #   ab[=LIBS]            interleaved A/B of lgm_amd/_lib/variants/lib_*.so (render: bench kernel times + output hashes)
 #   abattn               the same for the attention kernels (scripts/bench_attn.py)
-#   abmva[=LIBS]         bench.py --only-attn per variant library (MVAttention level, attention, cfg4)
+#   abmva[=LIBS]         bench.py --full --only-attn per variant library (MVAttention level, attention, cfg4)
 #   py=SCRIPT [ARGS]     python SCRIPT ARGS (a diagnostic under scripts/), output to $OUT/<script>.log
 #   tracepy=SCRIPT [ARGS]  rocprofv3 --kernel-trace --stats of python SCRIPT ARGS, split per grid (every kernel the
 #                        script launches, library GEMMs and torch's own included)
@@ -53,7 +53,7 @@ for step in "$@"; do
       rc=$?; echo "smoke_exit=$rc"; tail -2 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
       for r in $(seq 1 "${arg:-1}"); do
-        timeout -k 10 400 python bench.py > "$OUT/bench_plain$r.json" 2> "$OUT/bench_plain$r.err" || exit $?
+        timeout -k 10 400 python bench.py --full > "$OUT/bench_plain$r.json" 2> "$OUT/bench_plain$r.err" || exit $?
         summ "$OUT/bench_plain$r.json"
       done ;;
     benchargs)
@@ -62,7 +62,7 @@ for step in "$@"; do
       summ "$OUT/bench_args.json" 2>/dev/null || python -c "import json,sys;b=json.load(open(sys.argv[1]));print({k:(v if not isinstance(v,dict) else {kk:vv for kk,vv in v.items() if kk!=\"timed_loop\"}) for k,v in b.items()})" "$OUT/bench_args.json" ;;
     prof)
       mkdir -p "$OUT/prof" "$OUT/pmc"
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py > "$OUT/prof/bench.json" 2> "$OUT/prof/bench.err"
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full > "$OUT/prof/bench.json" 2> "$OUT/prof/bench.err"
       rc=$?; echo "stats rc=$rc"; [ $rc -eq 0 ] || exit $rc
       python scripts/kernel_stats_by_grid.py "$OUT/prof/run_kernel_trace.csv" > "$OUT/prof/kernel_stats_by_grid.txt"
       summ "$OUT/prof/bench.json"
@@ -70,7 +70,7 @@ for step in "$@"; do
       while read -r line; do
         [ -z "$line" ] && continue
         i=$((i+1))
-        timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $line -d "$OUT/pmc/p$i" -o run --output-format csv -- python bench.py --steps 3 --warmup 2 --only-pool --no-cpu-baseline > "$OUT/pmc/p$i.log" 2>&1
+        timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $line -d "$OUT/pmc/p$i" -o run --output-format csv -- python bench.py --full --steps 3 --warmup 2 --only-pool --no-cpu-baseline > "$OUT/pmc/p$i.log" 2>&1
         rc=$?; echo "pass $i ($line) rc=$rc"; [ $rc -eq 0 ] || exit $rc
       done < scripts/pmc_passes.txt
       python scripts/pmc_summary.py "$OUT/pmc" --json "$OUT/pmc_latest.json" > "$OUT/pmc_summary.txt"; echo "pmc summary rc=$?" ;;

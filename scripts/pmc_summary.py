@@ -64,7 +64,7 @@ if "--json" in sys.argv:  # per-dispatch HBM bytes for bench.py's roofline.traff
             rev = ""
     out["_meta"] = {"source": root, "commit": rev,
                     "workload": os.environ.get("PMC_WORKLOAD", "bench.py --only-pool (8-scene pool, cfg3 scenes)"),
-                    "command": "rocprofv3 --kernel-trace --pmc <pass> -- python bench.py --steps 3 --warmup 2 "
+                    "command": "rocprofv3 --kernel-trace --pmc <pass> -- python bench.py --full --steps 3 --warmup 2 "
                                "--only-pool --no-cpu-baseline"}
     path = sys.argv[sys.argv.index("--json") + 1]
     json.dump(out, open(path, "w"), indent=1)
