@@ -32,6 +32,16 @@ def needs_build() -> bool:
     return any(os.path.getmtime(p) > t for p in deps)
 
 
+def compile_cmd(src: str, obj: str, defines=()) -> list:
+    """The hipcc line that compiles one source (tests/test_bin_resources.py reads a kernel's resource usage from the
+    same line plus a remark flag)."""
+    extra = FILE_FLAGS.get(os.path.relpath(src, HERE), [])
+    return [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
+            "-munsafe-fp-atomics", "-fno-slp-vectorize", "-I", os.path.join(ROOT, "include"), "-I",
+            os.path.join(HERE, "csrc"), "-c", src, "-o", obj] + extra + \
+        [d if d.startswith("-") else f"-D{d}" for d in defines]  # A/B variants: defines or extra flags
+
+
 def build(force: bool = False, verbose: bool = False, out: str = None, defines=()) -> str:
     """Compile every source and link the shared library (`out` and `defines` build A/B variants)."""
     out = out or OUT
@@ -42,11 +52,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, defines=(
     tag = "" if out == OUT else "." + os.path.basename(out)
     for src in sources():
         obj = os.path.join(HERE, "_lib", os.path.basename(src) + tag + ".o")
-        extra = FILE_FLAGS.get(os.path.relpath(src, HERE), [])
-        cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
-               "-munsafe-fp-atomics", "-fno-slp-vectorize", "-I", os.path.join(ROOT, "include"), "-I",
-               os.path.join(HERE, "csrc"), "-c", src, "-o", obj] + extra + \
-            [d if d.startswith("-") else f"-D{d}" for d in defines]  # A/B variants: defines or extra flags
+        cmd = compile_cmd(src, obj, defines)
         if verbose:
             print(" ".join(cmd))
         cmds.append(cmd)

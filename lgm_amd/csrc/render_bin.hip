@@ -47,12 +47,26 @@ __device__ __forceinline__ int wave_incl_scan(int x, int /*lane*/) {
 // Gaussian found by a head-flag max-scan), so no lane idles behind a large Gaussian; a lane computes its row's exact
 // tile range (BinRec) and records the hits in an LDS hit list with their rank in the tile (returned by the
 // histogram atomic). The emission after the global reservation is a flat loop over that list.
-// A workgroup's BIN_ITERS batches are BIN_ITERS VIEWS of the same BIN_G Gaussians: each Gaussian row is loaded once
-// per workgroup instead of once per view (pool 199 -> 193 us, single scene 40.6 -> 38.8 us; 1 / 2 / 6 views per
-// workgroup measured slower).
+// A workgroup's BIN_ITERS batches are BIN_ITERS VIEWS of the same BIN_G Gaussians (1 / 2 / 6 views per workgroup
+// measured slower): the row is read and its 3D covariance computed once per workgroup, not per view.
+//
+// Occupancy: a workgroup is a chain of dependent phases (IEEE divisions and square roots, LDS round trips, one global
+// atomic round trip, five barriers per view) and overlaps none of them itself; only the other workgroups of its CU
+// do. The kernel every render runs (no statistics) therefore stays within 80 VGPRs, no scratch and 160 KiB / 3 of LDS
+// at 1,024 tiles: three workgroups per CU instead of two (tests/test_bin_resources.py holds the three figures). What
+// that took: Sigma held across the batches instead of the row's 14 values, the hit's tile rank folded into its sHit
+// word, and the statistics and stamps out of the way (k_bin). Pool 188 -> 161-163 us.
 constexpr int BIN_THREADS = 512, BIN_G = BIN_THREADS, BIN_ITERS = 3;
 constexpr int BIN_HITCAP = BIN_THREADS * 6;  // hit-list capacity (typical: ~4 hits per Gaussian)
-static_assert(BIN_THREADS <= 512, "owner index packs into 9 bits");
+static_assert(BIN_THREADS <= 512, "owner index and tile rank pack into 9 bits each");
+static_assert(LDS_HIST_MAX <= 1 << 13, "the tile index of a hit packs into 13 bits");
+// Waves per SIMD the compiler has to leave room for (amdgpu_waves_per_eu): 6, i.e. at most 80 VGPRs, without the
+// pair statistics (with stamps too: the stamped kernel measures the one every render runs); the statistics builds
+// keep 4 (they take 96-98 VGPRs).
+#ifndef LGM_BIN_WAVES  // (A/B: 4 = two workgroups per CU, as before)
+#define LGM_BIN_WAVES 6
+#endif
+constexpr int bin_waves(bool stats) { return stats ? 4 : LGM_BIN_WAVES; }
 
 // One Gaussian's emit record in LDS (48 B). The tiles a Gaussian can reach are found ROW BY ROW: for the tile row's
 // pixel band dy in [dy0, dy0 + BY - 1] the culling ellipse q = A dx^2 + 2B dx dy + C dy^2 <= tau spans
@@ -112,22 +126,25 @@ __device__ void center_order(int gx, int T, int *__restrict__ corder, int *hk) {
     for (int t = tid; t < T; t += BIN_THREADS) corder[atomicAdd(&hk[key(t)], 1)] = t;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__restrict__ gauss, const float *__restrict__ views,
-                                                     const float *__restrict__ projs, float4 *__restrict__ gP,
-                                                     float4 *__restrict__ gQ,
-                                                     uint2 *__restrict__ rects, int *__restrict__ radii_out,
-                                                     int *__restrict__ tile_count, const int *__restrict__ tile_start,
-                                                     unsigned long long *__restrict__ pairs, long long slot_stride,
-                                                     unsigned long long *__restrict__ misc, float *__restrict__ accum,
-                                                     int *__restrict__ corder) {
+// STATS: the pair statistics (misc[0..1] <- emitted and reference (Gaussian, tile) pair counts), read only through
+// stats_out and by the count-only pass. STAMPS: the per-workgroup phase stamps of lgm_diag.render_counters. Both
+// are compile-time: a training or inference render asks for neither, and their state (a 64-bit wave sum per view,
+// 64-bit stamp values live across the view loop) cost the production kernel a third workgroup per CU.
+template <int MODE, bool STATS, bool STAMPS>
+__global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin_waves(STATS)))) void k_bin(
+    Dims d, const float *__restrict__ gauss, const float *__restrict__ views, const float *__restrict__ projs,
+    float4 *__restrict__ gP, float4 *__restrict__ gQ, uint2 *__restrict__ rects, int *__restrict__ radii_out,
+    int *__restrict__ tile_count, const int *__restrict__ tile_start, unsigned long long *__restrict__ pairs,
+    long long slot_stride, unsigned long long *__restrict__ misc, float *__restrict__ accum,
+    int *__restrict__ corder) {
     extern __shared__ int hist[];  // [T] per-tile hit counts, [T] reserved global bases, [T] fallback cursors
     __shared__ BinRec srec[BIN_THREADS];
     __shared__ int sHead[BIN_THREADS], sExcl[BIN_THREADS];
-    __shared__ unsigned sHit[BIN_HITCAP];         // owner | tile << 9
-    __shared__ unsigned short sRank[BIN_HITCAP];  // rank of the hit within its tile (this workgroup)
+    // owner | rank << 9 | tile << 18: the rank of the hit within its tile (this workgroup, this view) is < BIN_G,
+    // because a Gaussian's rows hit a tile at most once
+    __shared__ unsigned sHit[BIN_HITCAP];
     __shared__ int s_nhit;
-    __shared__ unsigned long long s_tot[2];
+    __shared__ unsigned long long s_tot[2];  // (STATS)
     const int T = d.T, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int vgroups = (d.V + BIN_ITERS - 1) / BIN_ITERS;
     const int b = blockIdx.y / vgroups, vg0 = (blockIdx.y - b * vgroups) * BIN_ITERS;
@@ -135,32 +152,46 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
     const bool lds = T <= LDS_HIST_MAX;
     int *hbase = hist + T, *fill = hist + 2 * T;
     int *cur = tile_count + (size_t)bv * T;
-    if (tid < 2) s_tot[tid] = 0;
+    if constexpr (STATS)
+        if (tid < 2) s_tot[tid] = 0;
     auto dest = [&](int t, int pos) -> long long {
         return (MODE == EMIT_SLOT ? ((long long)bv * T + t) * slot_stride
                                   : (long long)tile_start[(size_t)bv * T + t]) + pos;
     };
     // diagnostics: per-workgroup phase stamps after the per-tile records (see lgm_diag.render_counters)
-    unsigned long long *stamp = d.counters ? d.counters + 8 + 8 * (size_t)d.BV * T +
-                                             8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x)
-                                           : nullptr;
     // (stamps: [0] start, [1..3] the summed durations of the preprocess, tile-test and reservation phases over the
     // batches, [4] end, [5] the last batch's hits)
-    unsigned long long t_ph = 0, ph_acc[3] = {0, 0, 0};
-    if (stamp && tid == 0) stamp[0] = t_ph = __builtin_amdgcn_s_memrealtime();
+    // Thread 0 keeps the running values in LDS (s_ph[0..2] the phase sums, s_ph[3] the last stamp), not in registers
+    // that would stay live across the batches: the stamped kernel then runs at the occupancy of the one it measures.
+    __shared__ unsigned long long s_ph[4];  // (STAMPS)
+    unsigned long long *stamp = nullptr;
+    if constexpr (STAMPS) {
+        stamp = d.counters + 8 + 8 * (size_t)d.BV * T + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+        if (tid == 0) {
+            s_ph[0] = s_ph[1] = s_ph[2] = 0;
+            stamp[0] = s_ph[3] = __builtin_amdgcn_s_memrealtime();
+        }
+    }
     auto phase = [&](int k) {
-        if (stamp && tid == 0) {
-            const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-            if (k >= 0) ph_acc[k] += t - t_ph;
-            t_ph = t;
+        if constexpr (STAMPS) {
+            if (tid == 0) {
+                const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+                if (k >= 0) s_ph[k] += t - s_ph[3];
+                s_ph[3] = t;
+            }
         }
     };
-    // BIN_ITERS batches per workgroup, one after the other: fewer, longer workgroups (2 per CU: 106 VGPRs at 8 waves
-    // per workgroup) fit the single scene's launch into one round of residency. The batches are views of the same
-    // Gaussians, whose rows are loaded once.
+    // BIN_ITERS batches per workgroup, one after the other: fewer, longer workgroups fit the single scene's launch
+    // into one round of residency. The batches are views of the same Gaussians: Sigma, which no view enters, is
+    // computed once and held (6 values); mean and opacity are read again for every view (16 B, an L2 hit) and not
+    // held (holding them too spills at 80 VGPRs).
     const int i = blockIdx.x * BIN_G + tid;
-    float g[14];
-    if (i < d.N) load_gaussian(gauss + ((size_t)b * d.N + i) * 14, g);
+    float c3[6];
+    if (i < d.N) {
+        float g[14];
+        load_gaussian(gauss + ((size_t)b * d.N + i) * 14, g);
+        gaussian_cov3d(g, d.mod, c3);
+    }
     for (int it = 0; it < BIN_ITERS; it++) {
     if (vg0 + it >= d.V) break;  // workgroup-uniform (the last view group of a scene may be short)
     bv = b * d.V + vg0 + it;
@@ -172,7 +203,10 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
     Geo o;
     bool vis = false;
     if (i < d.N) {
-        vis = preprocess_one(g, views + 16 * bv, projs + 16 * bv, d, o);
+        const float2 *gp = reinterpret_cast<const float2 *>(gauss + ((size_t)b * d.N + i) * 14);
+        const float2 g01 = gp[0], g23 = gp[1];
+        const float gm[4] = {g01.x, g01.y, g23.x, g23.y};
+        vis = preprocess_view(gm, c3, views + 16 * bv, projs + 16 * bv, d, o);
         if (MODE != COUNT) {
             const size_t k = (size_t)bv * d.N + i;
             if (vis) {
@@ -217,11 +251,13 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
         r.key = ((unsigned long long)__float_as_uint(o.depth) << 32) | (unsigned)i;
         srec[tid] = r;
         nc = o.cx1 > o.cx0 ? o.cy1 - o.cy0 : 0;  // candidate tile rows
-        nref = (unsigned long long)((o.x1 - o.x0) * (o.y1 - o.y0));
+        if constexpr (STATS) nref = (unsigned long long)((o.x1 - o.x0) * (o.y1 - o.y0));
     }
+    if constexpr (STATS) {
 #pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) nref += __shfl_xor(nref, o2, 64);
-    if (lane == 0 && nref) atomicAdd(&s_tot[1], nref);
+        for (int o2 = 32; o2 > 0; o2 >>= 1) nref += __shfl_xor(nref, o2, 64);
+        if (lane == 0 && nref) atomicAdd(&s_tot[1], nref);
+    }
     // ---- flattened (Gaussian, tile row) items of the wavefront: each lane finds its row's tile range
     const int incl = wave_incl_scan(nc, lane), excl = incl - nc;
     const int total = __builtin_amdgcn_readlane(incl, 63);
@@ -270,7 +306,7 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
         }
         const int hincl = wave_incl_scan(cnt, lane);
         const int htot = __builtin_amdgcn_readlane(hincl, 63);
-        nemit += (unsigned)htot;
+        if constexpr (STATS) nemit += (unsigned)htot;
         if (!htot) continue;
         if (lds) {
             int slot0 = 0;
@@ -281,10 +317,7 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
                 const int rk = atomicAdd(&hist[t], 1);
                 if (MODE != COUNT) {
                     const int slot = slot0 + k;
-                    if (slot < BIN_HITCAP) {
-                        sHit[slot] = (unsigned)owner | ((unsigned)t << 9);
-                        sRank[slot] = (unsigned short)rk;
-                    }
+                    if (slot < BIN_HITCAP) sHit[slot] = (unsigned)owner | ((unsigned)rk << 9) | ((unsigned)t << 18);
                 }
             }
         } else {
@@ -297,7 +330,8 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
     }
     };
     flat_tests(0);
-    if (lane == 0 && nemit) atomicAdd(&s_tot[0], nemit);
+    if constexpr (STATS)
+        if (lane == 0 && nemit) atomicAdd(&s_tot[0], nemit);
     if (lds) {
         __syncthreads();
         phase(1);
@@ -316,8 +350,8 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
             if (H <= BIN_HITCAP) {
                 for (int h = tid; h < H; h += BIN_THREADS) {
                     const unsigned e2 = sHit[h];
-                    const int t = (int)(e2 >> 9);
-                    pairs[dest(t, hbase[t] + sRank[h])] = srec[e2 & 511u].key;
+                    const int t = (int)(e2 >> 18);
+                    pairs[dest(t, hbase[t] + (int)((e2 >> 9) & 511u))] = srec[e2 & 511u].key;
                 }
             } else {
                 flat_tests(1);  // hit-list overflow: the wave's tests again, emitting with LDS fill ranks
@@ -326,21 +360,28 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(Dims d, const float *__rest
     }
     __syncthreads();
     phase(-1);  // (the emit phase: the rest of the batch)
-    if (stamp && tid == 0) {
-        stamp[1] = ph_acc[0];
-        stamp[2] = ph_acc[1];
-        stamp[3] = ph_acc[2];
-        stamp[4] = t_ph;
+    if (STAMPS && tid == 0) {
+        stamp[1] = s_ph[0];
+        stamp[2] = s_ph[1];
+        stamp[3] = s_ph[2];
+        stamp[4] = s_ph[3];
         stamp[5] = (unsigned long long)s_nhit;
         stamp[6] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID (SE / CU / SIMD / wave slot)
         stamp[7] = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // XCC_ID
     }
     }  // batches
-    if (tid == 0) {
+    if (STATS && tid == 0) {
         atomicAdd(&misc[0], s_tot[0]);
         atomicAdd(&misc[1], s_tot[1]);
     }
     if (corder && blockIdx.x == 0 && blockIdx.y == 0) center_order(d.gx, T, corder, hist);
+}
+
+// The k_bin instantiation of a launch (launch_binning).
+template <int MODE>
+auto bin_kernel(bool stats, bool stamps) {
+    return stats ? (stamps ? k_bin<MODE, true, true> : k_bin<MODE, true, false>)
+                 : (stamps ? k_bin<MODE, false, true> : k_bin<MODE, false, false>);
 }
 
 // k_scan: one workgroup of 1024 threads; exclusive scan of the M tile counts -> tile_start[0..M].
@@ -855,23 +896,29 @@ int launch_binning(const Dims &d, const float *gaussians, const float *cam_view,
     // hold its counting sort)
     int *corder = lds && d.T >= 8 ? (int *)(ws + L.order) : nullptr;
     dim3 grid((d.N + BIN_G - 1) / BIN_G, d.B * ((d.V + BIN_ITERS - 1) / BIN_ITERS));
+    // the pair statistics and the phase stamps are separate instantiations (k_bin): a render that asks for neither
+    // runs the kernel without their state
+    const bool stats = stats_out != nullptr || count_only, stamps = d.counters != nullptr;
     if (d.N > 0) {
         if (count_only || !L.slot) {
-            LGM_LAUNCH("k_bin_count", st, (k_bin<COUNT><<<grid, BIN_THREADS, lds, st>>>(d, gaussians, cam_view, cam_view_proj,
-                       gP, gQ, rects, nullptr, tcount, tstart, pairs, 0, misc, accum, nullptr)));
+            LGM_LAUNCH("k_bin_count", st, (bin_kernel<COUNT>(stats, stamps)<<<grid, BIN_THREADS, lds, st>>>(
+                       d, gaussians, cam_view, cam_view_proj, gP, gQ, rects, nullptr, tcount, tstart, pairs, 0, misc,
+                       accum, nullptr)));
         }
         if (!count_only) {
             if (L.slot) {
-                LGM_LAUNCH("k_bin", st, (k_bin<EMIT_SLOT><<<grid, BIN_THREADS, lds, st>>>(d, gaussians, cam_view, cam_view_proj,
-                           gP, gQ, rects, radii_out, tcount, tstart, pairs, (long long)d.N, misc, accum, corder)));
+                LGM_LAUNCH("k_bin", st, (bin_kernel<EMIT_SLOT>(stats, stamps)<<<grid, BIN_THREADS, lds, st>>>(
+                           d, gaussians, cam_view, cam_view_proj, gP, gQ, rects, radii_out, tcount, tstart, pairs,
+                           (long long)d.N, misc, accum, corder)));
             } else {
                 LGM_LAUNCH("k_scan", st, (k_scan<<<1, 1024, 0, st>>>(tcount, (int)M, tstart)));
                 if (hipMemsetAsync(ws + L.tile_count, 0, L.misc + 64 - L.tile_count, st) != hipSuccess) {
                     set_error("hipMemsetAsync failed");
                     return LGM_E_HIP;
                 }
-                LGM_LAUNCH("k_bin", st, (k_bin<EMIT_PACKED><<<grid, BIN_THREADS, lds, st>>>(d, gaussians, cam_view,
-                           cam_view_proj, gP, gQ, rects, radii_out, tcount, tstart, pairs, 0, misc, accum, corder)));
+                LGM_LAUNCH("k_bin", st, (bin_kernel<EMIT_PACKED>(stats, stamps)<<<grid, BIN_THREADS, lds, st>>>(
+                           d, gaussians, cam_view, cam_view_proj, gP, gQ, rects, radii_out, tcount, tstart, pairs, 0,
+                           misc, accum, corder)));
             }
             LGM_LAUNCH("k_sort", st, (k_sort<<<(unsigned)M, RS_THREADS, RS_LDS, st>>>(
                                          (int)M, L.slot ? (long long)d.N : -1LL, tstart, tcount, pairs, d.counters,

@@ -319,8 +319,20 @@ struct Geo {
 // {q <= tau} lies inside |dx| <= sqrt(tau a), |dy| <= sqrt(tau c) (a, c: the dilated 2D covariance), which
 // bounds the candidate tiles; the emitter then keeps a tile only if ellipse_hits_rect() says some pixel of it
 // can reach q <= tau. tau is inflated (below) so fp32 rounding of q can never re-admit a culled pixel.
-__device__ __forceinline__ bool preprocess_one(const float *g, const float *Vw, const float *Pm, const Dims &d,
-                                               Geo &o) {
+//
+// In two parts: gaussian_cov3d is the part no view enters (Sigma from the scales and the quaternion), computed once
+// per Gaussian; preprocess_view takes g[0..3] (mean, opacity) and Sigma for one view. Together they are the same
+// operations on the same operands in the same order as the one-piece form.
+__device__ __forceinline__ void gaussian_cov3d(const float *g, float mod, float c3[6]) {
+#pragma clang fp contract(off)
+    float R[3][3];
+    const float q[4] = {g[7], g[8], g[9], g[10]};
+    quat_rot(q, R);
+    const float s[3] = {mod * g[4], mod * g[5], mod * g[6]};
+    cov3d(s, R, c3);
+}
+__device__ __forceinline__ bool preprocess_view(const float *g, const float c3[6], const float *Vw, const float *Pm,
+                                                const Dims &d, Geo &o) {
 #pragma clang fp contract(off)
     float hom[4], pv[3];
     xf44(Pm, g[0], g[1], g[2], hom);
@@ -328,12 +340,6 @@ __device__ __forceinline__ bool preprocess_one(const float *g, const float *Vw, 
     const float ppx = hom[0] * pw, ppy = hom[1] * pw;
     xf43(Vw, g[0], g[1], g[2], pv);
     if (pv[2] <= 0.2f) return false;
-    float R[3][3];
-    const float q[4] = {g[7], g[8], g[9], g[10]};
-    quat_rot(q, R);
-    const float s[3] = {d.mod * g[4], d.mod * g[5], d.mod * g[6]};
-    float c3[6];
-    cov3d(s, R, c3);
     const ProjCtx P = make_proj(Vw, g[0], g[1], g[2], d.fx, d.fy, d.tanx, d.tany);
     float a, b, c;
     cov2d(P, c3, a, b, c);
