@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/lgm_render.h and include/lgm_attn.h (liblgm_amd.so).
+"""ctypes binding of the C ABI in include/*.h (liblgm_amd.so).
 
 There is no fallback: if the library is missing or cannot be loaded, every op raises. torch is imported first so
 that the library's NEEDED libamdhip64.so.7 resolves to the HIP runtime torch already loaded (same soname), giving
@@ -67,6 +67,12 @@ SIGNATURES = {
     "lgm_linear_wgrad_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
     "lgm_linear_wgrad": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp, _c_size,
                                   _vp, _vp]),
+    "lgm_gn_silu_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "lgm_gn_silu_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _c_size, _vp, _vp]),
+    "lgm_gn_silu_backward_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "lgm_gn_silu_backward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp, _vp]),
     "lgm_profiler_create": (_vp, []),
     "lgm_profiler_summary": (_c_int, [_vp, ctypes.c_char_p, _c_size]),
     "lgm_profiler_reset": (_c_int, [_vp]),
@@ -76,7 +82,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN

@@ -1,0 +1,85 @@
+"""infer.py's flow on lgm_amd alone (no reference checkout): an RGBA PNG -> 4 views + rays (the recipe of
+scripts/cfg1_cpu.load_views: the image composited on white and replicated to the four views MVDream would generate)
+-> native LGM ('big': lgm_amd.models.LGM on the fused GroupNorm+SiLU, attention, head and render kernels) -> save_ply
+and N orbit frames through lgm_amd.cameras.render_orbit_frames. Runs on the GPU or, with --device cpu, on the CPU
+(torch paths of lgm_amd/cpu.py). Without --ckpt the weights are a seeded random init (no checkpoint exists offline).
+
+    python scripts/lgm_infer.py [--png tests/golden/catstatue_rgba.png] [--ckpt STATE_DICT.pt] [--frames 8]
+                                [--device cuda|cpu] [--bf16] [--out bench_out_lgm_infer]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--png", default=os.path.join(ROOT, "tests", "golden", "catstatue_rgba.png"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "bench_out_lgm_infer"))
+    ap.add_argument("--ckpt", default=None, help="a state_dict file (torch.save) of LGM 'big'")
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--frames", type=int, default=8, help="orbit frames to render")
+    ap.add_argument("--render-size", type=int, default=256)
+    ap.add_argument("--bf16", action="store_true", help="run the model under bf16 autocast (GPU)")
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    if a.threads > 0:
+        torch.set_num_threads(a.threads)
+    from cfg1_cpu import load_views
+    from PIL import Image
+
+    from lgm_amd import LGM, preset
+    from lgm_amd.cameras import render_orbit_frames
+    dev = torch.device(a.device)
+    if dev.type == "cuda":
+        from lgm_amd import build as B
+        B.build()
+    opt = preset("big", output_size=a.render_size)
+    t = {}
+    t0 = time.perf_counter()
+    torch.manual_seed(a.seed)
+    model = LGM(opt)
+    if a.ckpt:
+        sd = torch.load(a.ckpt, map_location="cpu", weights_only=True)
+        model.load_state_dict(sd.get("model", sd) if isinstance(sd, dict) else sd, strict=True)
+    model = model.to(dev).eval()
+    t["build_s"] = time.perf_counter() - t0
+    images = load_views(a.png, opt.input_size).to(dev)  # [1, 4, 9, 256, 256]
+    with torch.no_grad():
+        t0 = time.perf_counter()
+        if a.bf16 and dev.type == "cuda":
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                gaussians = model.forward_gaussians(images)
+        else:
+            gaussians = model.forward_gaussians(images)
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+        t["model_s"] = time.perf_counter() - t0
+        os.makedirs(a.out, exist_ok=True)
+        ply = os.path.join(a.out, "catstatue.ply" if "catstatue" in a.png else "object.ply")
+        model.gs.save_ply(gaussians, ply)
+        t0 = time.perf_counter()
+        az = np.arange(a.frames, dtype=np.float64) * (360.0 / max(a.frames, 1))
+        frames = render_orbit_frames(model.gs, gaussians, az, radius=opt.cam_radius).cpu().numpy()
+        t["render_s"] = time.perf_counter() - t0
+    for i, f in enumerate(frames):
+        Image.fromarray(f).save(os.path.join(a.out, f"frame_{i:03d}.png"))
+    print(json.dumps({"device": str(dev), "gaussians": list(gaussians.shape), "finite": bool(torch.isfinite(gaussians).all()),
+                      "ply": ply, "ply_bytes": os.path.getsize(ply), "frames": list(frames.shape),
+                      "frame_mean": float(frames.mean()), "seconds": {k: round(v, 3) for k, v in t.items()}}))
+
+
+if __name__ == "__main__":
+    main()
