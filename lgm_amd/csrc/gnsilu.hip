@@ -21,25 +21,13 @@
 // 4 input pixels (NONE, UP2: 2 x 8 outputs) or 2 x 8 input pixels (DOWN2: 4 outputs); otherwise 1 input pixel or one
 // 2 x 2 input block. The _v / _s suffix of the kernel names (and 16 / 64 after it, the team) tells which form ran. Everything is written about
 // (x - mean): a large mean costs no precision (no E[x^2] - E[x]^2, no a x + b with b ~ -mean a).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
 #include <type_traits>
 
-#include "common.h"
-#include "lgm_attn.h"
+#include "elemwise.h"
 #include "lgm_norm.h"
 
 namespace lgm {
 namespace {
-
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(__hip_bfloat16 v) { return __bfloat162float(v); }
-__device__ __forceinline__ float to_f(__half v) { return __half2float(v); }
-template <class T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ __hip_bfloat16 from_f<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
-template <> __device__ __forceinline__ __half from_f<__half>(float v) { return __float2half(v); }
 
 constexpr int GNS_THREADS = 256;
 constexpr int GNS_CHUNK = 4096;     // elements per statistics workgroup (16 per thread, in registers)
@@ -47,16 +35,6 @@ constexpr int GNS_SLAB_MAX = 8192;  // elements of a (sample, group) slab the on
 constexpr int GNS_FILL = 256;       // workgroups that fill the chip (one per CU)
 constexpr int GNS_UNROLL = 4;       // items per thread of the elementwise passes
 constexpr int GNS_TILE = GNS_THREADS * GNS_UNROLL;  // items per workgroup of the elementwise passes
-
-__device__ __forceinline__ float block_sum256(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();  // red is reused between calls
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);  // fixed order: every thread gets the same value
-}
 
 // the sum over a team of LP consecutive lanes (16 or 64: shuffles inside the wave; 256: the workgroup), fixed order
 template <int LP>
@@ -70,35 +48,12 @@ __device__ __forceinline__ float team_sum(float v, float *red) {
     }
 }
 
-template <class T>
-__device__ __forceinline__ void ld4(const T *p, float *o) {
-    if constexpr (sizeof(T) == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-    } else {
-        T e[4];
-        *reinterpret_cast<uint2 *>(e) = *reinterpret_cast<const uint2 *>(p);
-#pragma unroll
-        for (int j = 0; j < 4; j++) o[j] = to_f(e[j]);
-    }
-}
-template <class T>
-__device__ __forceinline__ void st4(T *p, const float *v) {
-    if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        T e[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<uint2 *>(p) = *reinterpret_cast<const uint2 *>(e);
-    }
-}
 // WN consecutive elements: 4-element vectors where WN is a multiple of 4 (the caller guarantees the alignment)
 template <class T, int WN>
 __device__ __forceinline__ void ld_row(const T *p, float *o) {
     if constexpr (WN % 4 == 0) {
 #pragma unroll
-        for (int q = 0; q < WN / 4; q++) ld4<T>(p + 4 * q, o + 4 * q);
+        for (int q = 0; q < WN / 4; q++) load4<T>(p + 4 * q, o + 4 * q);
     } else {
 #pragma unroll
         for (int j = 0; j < WN; j++) o[j] = to_f(p[j]);
@@ -108,7 +63,7 @@ template <class T, int WN>
 __device__ __forceinline__ void st_row(T *p, const float *v) {
     if constexpr (WN % 4 == 0) {
 #pragma unroll
-        for (int q = 0; q < WN / 4; q++) st4<T>(p + 4 * q, v + 4 * q);
+        for (int q = 0; q < WN / 4; q++) store4<T>(p + 4 * q, v + 4 * q);
     } else {
 #pragma unroll
         for (int j = 0; j < WN; j++) p[j] = from_f<T>(v[j]);
@@ -230,7 +185,7 @@ __global__ __launch_bounds__(GNS_THREADS) void k_gns_slab(int C, int H, int W, i
     if constexpr (VEC) {  // n % 4 == 0, 16-byte aligned
         for (int i = tid; i < n / 4; i += GNS_THREADS) {
             float v[4];
-            ld4<TI>(xg + 4 * i, v);
+            load4<TI>(xg + 4 * i, v);
             *reinterpret_cast<float4 *>(slab + 4 * i) = make_float4(v[0], v[1], v[2], v[3]);
             s += (v[0] + v[1]) + (v[2] + v[3]);
         }
@@ -287,7 +242,7 @@ __global__ __launch_bounds__(GNS_THREADS) void k_gns_stats(size_t n, int S, cons
 #pragma unroll
         for (int k = 0; k < GNS_CHUNK / GNS_THREADS / 4; k++) {
             const int i = 4 * (k * GNS_THREADS + tid);
-            ld4<TI>(xc + (i < m ? i : 0), v + 4 * k);
+            load4<TI>(xc + (i < m ? i : 0), v + 4 * k);
         }
     } else {
 #pragma unroll
@@ -561,24 +516,17 @@ constexpr const char *DX_NAMES[2][3] = {{"k_gns_bwd_dx_s16", "k_gns_bwd_dx_s64",
                                         {"k_gns_bwd_dx_v16", "k_gns_bwd_dx_v64", "k_gns_bwd_dx_v"}};
 
 // the supported (x, y) dtype pairs: y's == x's, or fp32 x with any y
-template <class Fn>
-int with_pair(const char *who, int dtx, int dty, Fn &&fn) {
-    if (dtx == LGM_ATTN_F32) {
-        switch (dty) {
-            case LGM_ATTN_F32: return fn(float{}, float{});
-            case LGM_ATTN_BF16: return fn(float{}, __hip_bfloat16{});
-            case LGM_ATTN_F16: return fn(float{}, __half{});
-        }
-    } else if (dtx == dty) {
-        if (dtx == LGM_ATTN_BF16) return fn(__hip_bfloat16{}, __hip_bfloat16{});
-        if (dtx == LGM_ATTN_F16) return fn(__half{}, __half{});
-    }
-    set_error("%s: unsupported dtype pair x=%d y=%d (y's dtype must equal x's, or x be f32)", who, dtx, dty);
-    return LGM_E_INVALID;
-}
 bool pair_ok(int dtx, int dty) {
     const bool vy = dty == LGM_ATTN_F32 || dty == LGM_ATTN_BF16 || dty == LGM_ATTN_F16;
     return vy && (dtx == LGM_ATTN_F32 || (dtx == dty));
+}
+template <class Fn>
+int with_pair(const char *who, int dtx, int dty, Fn &&fn) {
+    if (!pair_ok(dtx, dty)) {
+        set_error("%s: unsupported dtype pair x=%d y=%d (y's dtype must equal x's, or x be f32)", who, dtx, dty);
+        return LGM_E_INVALID;
+    }
+    return with_type(who, dty, [&](auto ty) { return dtx == LGM_ATTN_F32 ? fn(float{}, ty) : fn(ty, ty); });
 }
 
 template <class Fn>

@@ -6,34 +6,20 @@
 //                in the qkv Linear's input dtype (bf16 under autocast): one launch instead of torch's moments /
 //                fused-params / normalise launches + the permute copy + the cast.
 //   k_mva_out    the [B, F*H*W, C] -> [B*F, C, H, W] permute of :45-46 fused with (x + res) * skip_scale of :47-48.
-// Both are HBM-bound layout kernels: 64x64 LDS-tiled transposes, so global reads and writes run along rows.
-#include <hip/hip_bf16.h>
+// and the backward's mirror of both (k_mva_out_bwd, k_mva_gn_part / k_mva_gn_coef / k_mva_gn_dx, below).
+// All are HBM-bound layout kernels. The tiled passes (k_mva_out, k_mva_out_bwd, k_mva_gn_part, k_mva_gn_dx) are
+// 64 x 64 LDS-tiled transposes, so global reads and writes run along rows; each is ONE kernel with a `bool VEC`
+// parameter, written on the two tile fragments ChanFrag / TokFrag: VEC reads channel rows 4 pixels and token rows
+// 8 channels per lane (C % 8 == 0, HW % 4 == 0, 16-B aligned tensors: mva_vec_ok; every LGM shape), the scalar form
+// takes single elements and serves ragged shapes. The two forms share the tile, the arithmetic and the summation
+// order: bitwise equal (tests/test_mva_forms_gpu.py).
 #include <initializer_list>
-#include <hip/hip_fp16.h>
+#include <type_traits>
 
-#include "common.h"
-#include "lgm_attn.h"
+#include "elemwise.h"
 
 namespace lgm {
 namespace {
-
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(__hip_bfloat16 v) { return __bfloat162float(v); }
-__device__ __forceinline__ float to_f(__half v) { return __half2float(v); }
-template <class T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ __hip_bfloat16 from_f<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
-template <> __device__ __forceinline__ __half from_f<__half>(float v) { return __float2half(v); }
-
-__device__ __forceinline__ float block_sum256(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();  // red is reused between calls
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);  // fixed order: every thread gets the same value
-}
 
 // GroupNorm statistics in two launches, all deterministic:
 // k_mva_stats  grid (S, G, B*F): chunk s of group g of sample bf (the group's Cg*HW elements are contiguous) ->
@@ -142,14 +128,16 @@ __global__ __launch_bounds__(256) void k_mva_norm(int F, int C, int HW, int G, f
 constexpr int GN_THREADS = 512;
 constexpr size_t GN_LDS_MAX = 144 * 1024;  // bytes of dynamic LDS the fused form may take
 
-__device__ __forceinline__ float block_sum512(float v, float *red) {
+// 8 consecutive channels of a token row: one 16-B store at 16 bits; fp32 stays 8 scalar stores (the token pointer's
+// 32-B alignment is not checked on the forward GroupNorm paths)
+template <class TO>
+__device__ __forceinline__ void store_tok8(TO *dst, const float (&v)[8]) {
+    if constexpr (sizeof(TO) == 2) {
+        store8<TO>(dst, v);
+    } else {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();  // red is reused between calls
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));  // fixed order
+        for (int j = 0; j < 8; j++) dst[j] = v[j];
+    }
 }
 
 template <class TI, class TO>
@@ -224,16 +212,10 @@ __global__ __launch_bounds__(GN_THREADS) void k_mva_gn_tok(int F, int C, int HW,
         const int c8n = Cg / 8;
         for (int p = tid; p < HW * c8n; p += GN_THREADS) {
             const int hw = p / c8n, c0 = (p - hw * c8n) * 8;
-            TO o[8];
+            float o[8];
 #pragma unroll
-            for (int j = 0; j < 8; j++) o[j] = from_f<TO>(fmaf(slab[(c0 + j) * HW + hw], sa[c0 + j], sb[c0 + j]));
-            TO *dst = tb + (size_t)hw * C + c0;
-            if constexpr (sizeof(TO) == 2) {
-                *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(o);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; j++) dst[j] = o[j];
-            }
+            for (int j = 0; j < 8; j++) o[j] = fmaf(slab[(c0 + j) * HW + hw], sa[c0 + j], sb[c0 + j]);
+            store_tok8<TO>(tb + (size_t)hw * C + c0, o);
         }
     } else {
         for (int p = tid; p < HW * Cg; p += GN_THREADS) {
@@ -253,19 +235,6 @@ __global__ __launch_bounds__(GN_THREADS) void k_mva_gn_tok(int F, int C, int HW,
 //               Against k_mva_gn_tok: bench level 31.8 -> 29.5 us, cfg4 184.4 -> 153.3 us per pass (its C = 512 level
 //               has 192 workgroups: all loads in flight at once matters most there; profiles/r05/ab_mva_gn_reg).
 constexpr int GNR_K = 2;  // items per thread (64 registers of slab)
-template <class TI>
-__device__ __forceinline__ void load4(const TI *p, float (&o)[4]) {
-    if constexpr (sizeof(TI) == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-    } else {
-        const uint2 t = *reinterpret_cast<const uint2 *>(p);
-        TI e[4];
-        *reinterpret_cast<uint2 *>(e) = t;
-#pragma unroll
-        for (int j = 0; j < 4; j++) o[j] = to_f(e[j]);
-    }
-}
 template <class TI, class TO>
 __global__ __launch_bounds__(GN_THREADS) void k_mva_gn_reg(int F, int C, int HW, int G, float eps,
                                                             const TI *__restrict__ x, const float *__restrict__ gamma,
@@ -333,240 +302,206 @@ __global__ __launch_bounds__(GN_THREADS) void k_mva_gn_reg(int F, int C, int HW,
             }
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                TO o[8];
+                float o[8];
 #pragma unroll
-                for (int j = 0; j < 8; j++) o[j] = from_f<TO>(fmaf(v[k][j][e], a8[j], b8[j]));
-                TO *dst = tb + (size_t)(4 * p4 + e) * C + 8 * cb;
-                if constexpr (sizeof(TO) == 2) {
-                    *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<const uint4 *>(o);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; j++) dst[j] = o[j];
-                }
+                for (int j = 0; j < 8; j++) o[j] = fmaf(v[k][j][e], a8[j], b8[j]);
+                store_tok8<TO>(tb + (size_t)(4 * p4 + e) * C + 8 * cb, o);
             }
         }
     }
 }
 
-// grid (ceil(HW/64), ceil(C/64), B*F), block 256: out[bf][c][hw] = (y[b][f HW + hw][c] + res[bf][c][hw]) * skip
-// through a 64 x 64 LDS tile (reads along c, writes along hw). In a lower-precision output the sum is rounded
-// before the scale, as torch's two ops do.
-template <class TY, class TR, class TO>
+// ---- the tiled passes: grid (ceil(HW/64), ceil(C/64), B*F), block 256, one 64-channel x 64-pixel tile per workgroup.
+// A fragment is a thread's 16 elements of that tile in the order of its global accesses: ChanFrag along hw (the
+// [B*F, C, HW] tensors), TokFrag along c (the [B, F*HW, C] tokens). at(n, t) places element v[n]; load only issues
+// loads, every one unconditional (lanes outside the tensor on a clamped in-range address, their values never used:
+// masking happens at put / store), so all loads of a kernel go out before its first wait; put writes the fragment to
+// the [64][65] LDS tile in its own orientation, zero outside the tensor; store is masked.
+struct Tile {
+    int F, C, HW, bf, hw0, c0;
+};
+__device__ __forceinline__ Tile this_tile(int F, int C, int HW) {
+    return {F, C, HW, (int)blockIdx.z, (int)blockIdx.x * 64, (int)blockIdx.y * 64};
+}
+struct Pos {
+    int r, j;  // row of the fragment's orientation, position along it
+    bool ok;   // inside the tensor
+};
+
+// VEC: 4 accesses of 4 pixels (channel row i >> 4, pixels 4 (i & 15) ..); scalar: 16 of 1 (row i >> 6, pixel i & 63)
+template <bool VEC>
+struct ChanFrag {
+    static constexpr int W = VEC ? 4 : 1;
+    float v[16];
+    static __device__ __forceinline__ Pos at(int n, const Tile &t) {  // r: channel, j: pixel
+        const int i = threadIdx.x + 256 * (n / W);
+        const int r = VEC ? i >> 4 : i >> 6, h = VEC ? 4 * (i & 15) + n % W : i & 63;
+        return {r, h, t.c0 + r < t.C && t.hw0 + h < t.HW};
+    }
+    static __device__ __forceinline__ size_t offset(const Pos &p, const Tile &t) {
+        return ((size_t)t.bf * t.C + t.c0 + p.r) * t.HW + t.hw0 + p.j;
+    }
+    template <class T>
+    __device__ __forceinline__ void load(const T *__restrict__ x, const Tile &t) {
+#pragma unroll
+        for (int n = 0; n < 16; n += W) {
+            const Pos p = at(n, t);
+            const T *src = x + (p.ok ? offset(p, t) : 0);
+            if constexpr (VEC) load4<T>(src, v + n);
+            else v[n] = to_f(*src);
+        }
+    }
+    template <class T>
+    __device__ __forceinline__ void store1(T *__restrict__ x, const Tile &t, int n) const {  // the access at v[n]
+        const Pos p = at(n, t);
+        if (!p.ok) return;
+        if constexpr (VEC) store4<T>(x + offset(p, t), v + n);
+        else x[offset(p, t)] = from_f<T>(v[n]);
+    }
+    template <class T>
+    __device__ __forceinline__ void store(T *__restrict__ x, const Tile &t) const {
+#pragma unroll
+        for (int n = 0; n < 16; n += W) store1(x, t, n);
+    }
+    __device__ __forceinline__ void put(float (&tile)[64][65], const Tile &t) const {  // [channel][pixel]
+#pragma unroll
+        for (int n = 0; n < 16; n++) {
+            const Pos p = at(n, t);
+            tile[p.r][p.j] = p.ok ? v[n] : 0.f;
+        }
+    }
+};
+
+// VEC: 2 accesses of 8 channels (token row i >> 3, channels 8 (i & 7) ..); scalar: 16 of 1 (row i >> 6, channel i & 63)
+template <bool VEC>
+struct TokFrag {
+    static constexpr int W = VEC ? 8 : 1;
+    float v[16];
+    static __device__ __forceinline__ Pos at(int n, const Tile &t) {  // r: token row (pixel), j: channel
+        const int i = threadIdx.x + 256 * (n / W);
+        const int r = VEC ? i >> 3 : i >> 6, c = VEC ? 8 * (i & 7) + n % W : i & 63;
+        return {r, c, t.hw0 + r < t.HW && t.c0 + c < t.C};
+    }
+    static __device__ __forceinline__ size_t offset(const Pos &p, const Tile &t) {
+        const int b = t.bf / t.F, f = t.bf - b * t.F;
+        return ((size_t)b * t.F * t.HW + (size_t)f * t.HW + t.hw0 + p.r) * t.C + t.c0 + p.j;
+    }
+    template <class T>
+    __device__ __forceinline__ void load(const T *__restrict__ tok, const Tile &t) {
+#pragma unroll
+        for (int n = 0; n < 16; n += W) {
+            const Pos p = at(n, t);
+            const T *src = tok + (p.ok ? offset(p, t) : 0);
+            if constexpr (VEC) load8<T>(src, v + n);
+            else v[n] = to_f(*src);
+        }
+    }
+    template <class T>
+    __device__ __forceinline__ void store(T *__restrict__ tok, const Tile &t) const {
+#pragma unroll
+        for (int n = 0; n < 16; n += W) {
+            const Pos p = at(n, t);
+            if (!p.ok) continue;
+            if constexpr (VEC) store8<T>(tok + offset(p, t), v + n);
+            else tok[offset(p, t)] = from_f<T>(v[n]);
+        }
+    }
+    __device__ __forceinline__ void put(float (&tile)[64][65], const Tile &t) const {  // [pixel][channel]
+#pragma unroll
+        for (int n = 0; n < 16; n++) {
+            const Pos p = at(n, t);
+            tile[p.r][p.j] = p.ok ? v[n] : 0.f;
+        }
+    }
+};
+
+// k_mva_out: out[bf][c][hw] = (y[b][f HW + hw][c] + res[bf][c][hw]) * skip (reads along c, writes along hw); the
+// residual's loads go out with the tokens' (one round trip). In a lower-precision output the sum is rounded before
+// the scale, as torch's two ops do. Vector against scalar accesses: bench level 37.0 -> 31.2 us, cfg4 171.6 ->
+// 141.0 us per pass (profiles/r05/ab_mva_vec).
+template <class TY, class TR, class TO, bool VEC>
 __global__ __launch_bounds__(256) void k_mva_out(int F, int C, int HW, const TY *__restrict__ y,
                                                  const TR *__restrict__ res, float skip, TO *__restrict__ out) {
-    __shared__ float tile[64][65];
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    const int b = bf / F, f = bf - b * F;
-    const TY *yb = y + ((size_t)b * F * HW + (size_t)f * HW) * C;
-    float v[16];
+    __shared__ float tile[64][65];  // [channel][pixel]
+    const Tile t = this_tile(F, C, HW);
+    TokFrag<VEC> yv;
+    ChanFrag<VEC> ov;  // the residual, then the output
+    yv.load(y, t);
+    if (res) ov.load(res, t);
 #pragma unroll
-    for (int k = 0; k < 16; k++) {  // all loads in flight before the first use (clamped, unconditional addresses)
-        const int i = tid + 256 * k, r = i >> 6, c = i & 63;  // token row r, channel c
-        const bool ok = hw0 + r < HW && c0 + c < C;
-        v[k] = to_f(yb[ok ? (size_t)(hw0 + r) * C + c0 + c : 0]);
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, c = i & 63;
-        tile[c][r] = v[k];
-    }
-    float rv[16];
-    if (res) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const int i = tid + 256 * k, r = i >> 6, h = i & 63;  // channel r, pixel h
-            const bool ok = hw0 + h < HW && c0 + r < C;
-            rv[k] = to_f(res[ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + h : 0]);
-        }
+    for (int n = 0; n < 16; n++) {
+        const Pos p = TokFrag<VEC>::at(n, t);
+        tile[p.j][p.r] = yv.v[n];
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, h = i & 63;  // channel r, pixel h
-        if (hw0 + h < HW && c0 + r < C) {
-            const size_t o = ((size_t)bf * C + c0 + r) * HW + hw0 + h;
-            float t = tile[r][h];
-            if (res) {
-                t += rv[k];
-                t = to_f(from_f<TO>(t));  // (exact for an fp32 output)
-                t *= skip;
-            }
-            out[o] = from_f<TO>(t);
-        }
-    }
-}
-
-template <class T>
-__device__ __forceinline__ void load8(const T *p, float (&o)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    } else {
-        T e[8];
-        *reinterpret_cast<uint4 *>(e) = *reinterpret_cast<const uint4 *>(p);
-#pragma unroll
-        for (int j = 0; j < 8; j++) o[j] = to_f(e[j]);
-    }
-}
-template <class T>
-__device__ __forceinline__ void store4(T *p, const float (&v)[4]) {
-    if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        T e[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<uint2 *>(p) = *reinterpret_cast<const uint2 *>(e);
-    }
-}
-// k_mva_out with vector accesses (C % 8 == 0, HW % 4 == 0, 16-B aligned tensors): the tokens read 8 channels per
-// lane (16 B at 16 bits), the residual read and the output written 4 pixels per lane; the residual's loads go out
-// with the tokens' (one round trip). Same arithmetic, bitwise equal. Against k_mva_out: bench level 37.0 -> 31.2 us,
-// cfg4 171.6 -> 141.0 us per pass (profiles/r05/ab_mva_vec).
-template <class TY, class TR, class TO>
-__global__ __launch_bounds__(256) void k_mva_out_v(int F, int C, int HW, const TY *__restrict__ y,
-                                                   const TR *__restrict__ res, float skip, TO *__restrict__ out) {
-    __shared__ float tile[64][65];
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    const int b = bf / F, f = bf - b * F;
-    const TY *yb = y + ((size_t)b * F * HW + (size_t)f * HW) * C;
-    float v[2][8], rv[4][4];
-    // every load unconditional, out-of-range lanes on a clamped in-range address (their values are never used), so
-    // all six go out before the first wait
-#pragma unroll
-    for (int k = 0; k < 2; k++) {  // token row r, channels 8 q .. 8 q + 7
-        const int i = tid + 256 * k, r = i >> 3, q = i & 7;
-        const bool ok = hw0 + r < HW && c0 + 8 * q < C;
-        load8<TY>(yb + (ok ? (size_t)(hw0 + r) * C + c0 + 8 * q : 0), v[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {  // channel row r, pixels 4 p .. 4 p + 3
-        const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-        const bool ok = c0 + r < C && hw0 + 4 * p < HW;
+    for (int n = 0; n < 16; n++) {
+        const Pos p = ChanFrag<VEC>::at(n, t);
+        float s = tile[p.r][p.j];
         if (res) {
-            const TR *src = res + (ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p : 0);
-            if constexpr (sizeof(TR) == 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(src);
-                rv[k][0] = a.x; rv[k][1] = a.y; rv[k][2] = a.z; rv[k][3] = a.w;
-            } else {
-                TR e[4];
-                *reinterpret_cast<uint2 *>(e) = *reinterpret_cast<const uint2 *>(src);
-#pragma unroll
-                for (int j = 0; j < 4; j++) rv[k][j] = to_f(e[j]);
-            }
+            s += ov.v[n];
+            s = to_f(from_f<TO>(s));  // (exact for an fp32 output)
+            s *= skip;
         }
+        ov.v[n] = s;
     }
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int i = tid + 256 * k, r = i >> 3, q = i & 7;
-#pragma unroll
-        for (int j = 0; j < 8; j++) tile[8 * q + j][r] = v[k][j];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-        if (c0 + r < C && hw0 + 4 * p < HW) {
-            float o4[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                float t = tile[r][4 * p + e];
-                if (res) {
-                    t += rv[k][e];
-                    t = to_f(from_f<TO>(t));  // (exact for an fp32 output)
-                    t *= skip;
-                }
-                o4[e] = t;
-            }
-            store4<TO>(out + ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p, o4);
-        }
-    }
+    ov.store(out, t);
 }
 
 // ---- backward (core/unet.py:40-48 backward), the mirror of the two passes above:
-// k_mva_out_bwd   grid (ceil(HW/64), ceil(C/64), B*F): g = dL/dout * scale (rounded to out's dtype, as torch's
-//                 `d_out * skip`), written to d_res [B*F, C, H, W] along hw and, through the 64 x 64 LDS tile, to the
-//                 tokens' gradient d_y [B, F*H*W, C] along c.
-// k_mva_gn_part   grid (ceil(HW/64), ceil(C/64), B*F): per (sample, channel, 64-pixel tile) partial sums of
-//                 dy * x and dy (dy = the token gradient read back through the LDS tile) -> part2
+// k_mva_out_bwd   g = dL/dout * scale (rounded to out's dtype, as torch's `d_out * skip`), written to d_res
+//                 [B*F, C, H, W] along hw and, through the LDS tile, to the tokens' gradient d_y [B, F*H*W, C] along c.
+// k_mva_gn_part   per (sample, channel, 64-pixel tile) partial sums of dy * x and dy (dy = the token gradient read
+//                 back through the LDS tile) -> part2
 // k_mva_gn_coef   grid (G): per (sample, channel) ds = sum dy x, db = sum dy (fixed order over the tiles), then per
 //                 (sample, group) torch's fused backward parameters c2, c3 and per channel dgamma, dbeta (fixed
 //                 order over the samples): deterministic
-// k_mva_gn_dx     grid (ceil(HW/64), ceil(C/64), B*F): dx = rstd gamma dy + c2 x + c3 (+ d_res), one rounding to
-//                 x's dtype: the GroupNorm backward and autograd's sum with the residual's gradient in one pass.
-template <class TD, class TY, class TR>
+// k_mva_gn_dx     dx = rstd gamma dy + c2 x + c3 (+ d_res), one rounding to x's dtype: the GroupNorm backward and
+//                 autograd's sum with the residual's gradient in one pass.
+// Vector against scalar accesses, bench level (C = 512, 32 x 32, 32 samples): k_mva_out_bwd 36.0 -> 31.8 us,
+// k_mva_gn_part 25.3 -> 23.3 us, k_mva_gn_dx 40.8 -> 40.2 us (profiles/r05/ab_mva_vecb).
+template <class TD, class TY, class TR, bool VEC>
 __global__ __launch_bounds__(256) void k_mva_out_bwd(int F, int C, int HW, const TD *__restrict__ dout, float scale,
                                                      TY *__restrict__ dy, TR *__restrict__ dres) {
     __shared__ float tile[64][65];  // [channel][pixel]
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    float v[16];
+    const Tile t = this_tile(F, C, HW);
+    ChanFrag<VEC> g;
+    g.load(dout, t);
 #pragma unroll
-    for (int k = 0; k < 16; k++) {  // all loads in flight before the first use (clamped, unconditional addresses)
-        const int i = tid + 256 * k, r = i >> 6, h = i & 63;  // channel r, pixel h
-        const bool ok = hw0 + h < HW && c0 + r < C;
-        v[k] = to_f(dout[ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + h : 0]);
-    }
+    for (int n0 = 0; n0 < 16; n0 += ChanFrag<VEC>::W) {  // per access: its d_res store goes out once its load is back
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, h = i & 63;
-        const float g = to_f(from_f<TD>(v[k] * scale));  // (exact: scale 1 and an fp32 gradient)
-        tile[r][h] = g;
-        if (dres && hw0 + h < HW && c0 + r < C) dres[((size_t)bf * C + c0 + r) * HW + hw0 + h] = from_f<TR>(g);
+        for (int n = n0; n < n0 + ChanFrag<VEC>::W; n++) {
+            const Pos p = ChanFrag<VEC>::at(n, t);
+            g.v[n] = to_f(from_f<TD>(g.v[n] * scale));  // (exact: scale 1 and an fp32 gradient)
+            tile[p.r][p.j] = g.v[n];
+        }
+        if (dres) g.store1(dres, t, n0);
     }
     __syncthreads();
-    const int b = bf / F, f = bf - b * F;
-    TY *yb = dy + ((size_t)b * F * HW + (size_t)f * HW) * C;
+    TokFrag<VEC> dv;
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, c = i & 63;  // token row r, channel c
-        if (hw0 + r < HW && c0 + c < C) yb[(size_t)(hw0 + r) * C + c0 + c] = from_f<TY>(tile[c][r]);
+    for (int n = 0; n < 16; n++) {
+        const Pos p = TokFrag<VEC>::at(n, t);
+        dv.v[n] = tile[p.j][p.r];
     }
+    dv.store(dy, t);
 }
 
-// the token gradient of a 64-channel x 64-pixel tile into LDS as [pixel][channel] (reads along c), zero outside
-template <class TT>
-__device__ __forceinline__ void load_tok_tile(float (&tile)[64][65], const TT *__restrict__ tok, int F, int C, int HW,
-                                              int bf, int hw0, int c0) {
-    const int b = bf / F, f = bf - b * F, tid = threadIdx.x;
-    const TT *tb = tok + ((size_t)b * F * HW + (size_t)f * HW) * C;
-    float v[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, c = i & 63;  // token row r, channel c
-        const bool ok = hw0 + r < HW && c0 + c < C;
-        v[k] = to_f(tb[ok ? (size_t)(hw0 + r) * C + c0 + c : 0]);
-        v[k] = ok ? v[k] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, c = i & 63;
-        tile[r][c] = v[k];
-    }
-}
-
-template <class TI, class TT>
+template <class TI, class TT, bool VEC>
 __global__ __launch_bounds__(256) void k_mva_gn_part(int F, int C, int HW, const TI *__restrict__ x,
                                                      const TT *__restrict__ dtok, float2 *__restrict__ part) {
     __shared__ float tile[64][65];  // dy [pixel][channel]
     __shared__ float xs[64][65];    // x [channel][pixel]
     __shared__ float2 red[4][64];
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    const int nT = gridDim.x;
+    const Tile t = this_tile(F, C, HW);
+    const int tid = threadIdx.x, nT = gridDim.x;
     {
-        float xv[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) {  // x along hw (zero outside), issued before the token tile's loads
-            const int i = tid + 256 * k, r = i >> 6, h = i & 63;  // channel r, pixel h
-            const bool ok = hw0 + h < HW && c0 + r < C;
-            xv[k] = to_f(x[ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + h : 0]);
-            xv[k] = ok ? xv[k] : 0.f;
-        }
-        load_tok_tile(tile, dtok, F, C, HW, bf, hw0, c0);
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const int i = tid + 256 * k, r = i >> 6, h = i & 63;
-            xs[r][h] = xv[k];
-        }
+        ChanFrag<VEC> xv;
+        TokFrag<VEC> dv;
+        xv.load(x, t);
+        dv.load(dtok, t);
+        xv.put(xs, t);
+        dv.put(tile, t);
     }
     __syncthreads();
     // thread: channel c = tid & 63, pixels 16 q .. 16 q + 15 (q = the wave); the four quarters summed in order
@@ -581,9 +516,9 @@ __global__ __launch_bounds__(256) void k_mva_gn_part(int F, int C, int HW, const
     }
     red[q][c] = make_float2(sdx, sd);
     __syncthreads();
-    if (tid < 64 && c0 + tid < C) {
+    if (tid < 64 && t.c0 + tid < C) {
         const float2 a = red[0][tid], b2 = red[1][tid], c2 = red[2][tid], d2 = red[3][tid];
-        part[((size_t)bf * C + c0 + tid) * nT + blockIdx.x] =
+        part[((size_t)t.bf * C + t.c0 + tid) * nT + blockIdx.x] =
             make_float2((a.x + b2.x) + (c2.x + d2.x), (a.y + b2.y) + (c2.y + d2.y));
     }
 }
@@ -665,217 +600,53 @@ __global__ __launch_bounds__(256) void k_mva_gn_coef(int BF, int C, int HW, int 
     }
 }
 
-template <class TI, class TT, class TR>
+template <class TI, class TT, class TR, bool VEC>
 __global__ __launch_bounds__(256) void k_mva_gn_dx(int F, int C, int HW, int G, const TI *__restrict__ x,
                                                    const TT *__restrict__ dtok, const TR *__restrict__ dres,
                                                    const float *__restrict__ gamma, const float *__restrict__ rstd,
                                                    const float2 *__restrict__ coef, TI *__restrict__ dx) {
     __shared__ float tile[64][65];  // [pixel][channel]
     __shared__ float sa[64], sb[64], sc[64];
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    const int Cg = C / G;
-    if (tid < 64 && c0 + tid < C) {
-        const int c = c0 + tid, g = c / Cg;
-        const float2 k = coef[(size_t)bf * G + g];
-        sa[tid] = rstd[(size_t)bf * G + g] * (gamma ? gamma[c] : 1.f);
+    const Tile t = this_tile(F, C, HW);
+    const int tid = threadIdx.x, Cg = C / G;
+    TokFrag<VEC> dv;
+    ChanFrag<VEC> xv, rv;  // xv: x, then dx
+    dv.load(dtok, t);
+    xv.load(x, t);
+    if (dres) {
+        rv.load(dres, t);
+    } else {
+#pragma unroll
+        for (int n = 0; n < 16; n++) rv.v[n] = 0.f;
+    }
+    if (tid < 64 && t.c0 + tid < C) {
+        const int c = t.c0 + tid, g = c / Cg;
+        const float2 k = coef[(size_t)t.bf * G + g];
+        sa[tid] = rstd[(size_t)t.bf * G + g] * (gamma ? gamma[c] : 1.f);
         sb[tid] = k.x;
         sc[tid] = k.y;
     }
-    load_tok_tile(tile, dtok, F, C, HW, bf, hw0, c0);
-    float xv[16], rv[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {  // x and the residual's gradient along hw, all in flight before the barrier
-        const int i = tid + 256 * k, r = i >> 6, h = i & 63;  // channel r, pixel h
-        const bool ok = hw0 + h < HW && c0 + r < C;
-        const size_t o = ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + h : 0;
-        xv[k] = to_f(x[o]);
-        rv[k] = dres ? to_f(dres[o]) : 0.f;
-    }
+    dv.put(tile, t);
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int i = tid + 256 * k, r = i >> 6, h = i & 63;
-        if (hw0 + h < HW && c0 + r < C) {
-            const float v = fmaf(sa[r], tile[h][r], fmaf(sb[r], xv[k], sc[r])) + rv[k];
-            dx[((size_t)bf * C + c0 + r) * HW + hw0 + h] = from_f<TI>(v);
-        }
+    for (int n = 0; n < 16; n++) {
+        const Pos p = ChanFrag<VEC>::at(n, t);
+        xv.v[n] = fmaf(sa[p.r], tile[p.j][p.r], fmaf(sb[p.r], xv.v[n], sc[p.r])) + rv.v[n];
     }
+    xv.store(dx, t);
 }
 
-// ---- vector-access forms of the three backward layout kernels (C % 8 == 0, HW % 4 == 0, 16-B aligned tensors):
-// channel rows read / written 4 pixels per lane, token rows 8 channels per lane, every load in flight before the
-// first wait; the same arithmetic and summation order as the scalar forms (bitwise equal). Bench level (C = 512,
-// 32 x 32, 32 samples): k_mva_out_bwd 36.0 -> 31.8 us, k_mva_gn_part 25.3 -> 23.3 us, k_mva_gn_dx 40.8 -> 40.2 us
-// (profiles/r05/ab_mva_vecb).
-template <class T>
-__device__ __forceinline__ void store8(T *p, const float (&v)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        reinterpret_cast<float4 *>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4 *>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-        T e[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<uint4 *>(p) = *reinterpret_cast<const uint4 *>(e);
-    }
-}
-template <class TD, class TY, class TR>
-__global__ __launch_bounds__(256) void k_mva_out_bwd_v(int F, int C, int HW, const TD *__restrict__ dout, float scale,
-                                                       TY *__restrict__ dy, TR *__restrict__ dres) {
-    __shared__ float tile[64][65];  // [channel][pixel]
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    float v[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {  // channel row r, pixels 4 p .. 4 p + 3
-        const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-        const bool ok = c0 + r < C && hw0 + 4 * p < HW;
-        load4<TD>(dout + (ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p : 0), v[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-        float g[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            g[e] = to_f(from_f<TD>(v[k][e] * scale));  // (exact: scale 1 and an fp32 gradient)
-            tile[r][4 * p + e] = g[e];
-        }
-        if (dres && c0 + r < C && hw0 + 4 * p < HW) store4<TR>(dres + ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p, g);
-    }
-    __syncthreads();
-    const int b = bf / F, f = bf - b * F;
-    TY *yb = dy + ((size_t)b * F * HW + (size_t)f * HW) * C;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {  // token row r, channels 8 q .. 8 q + 7
-        const int i = tid + 256 * k, r = i >> 3, q = i & 7;
-        if (hw0 + r < HW && c0 + 8 * q < C) {
-            float o[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) o[j] = tile[8 * q + j][r];
-            store8<TY>(yb + (size_t)(hw0 + r) * C + c0 + 8 * q, o);
-        }
-    }
-}
-// the token gradient tile into LDS as [pixel][channel], zero outside (the loads only issued here; the caller's
-// other loads can go out before the stores to LDS)
-template <class TT>
-struct TokTileV {
-    float v[2][8];
-    __device__ __forceinline__ void load(const TT *__restrict__ tok, int F, int C, int HW, int bf, int hw0, int c0) {
-        const int b = bf / F, f = bf - b * F, tid = threadIdx.x;
-        const TT *tb = tok + ((size_t)b * F * HW + (size_t)f * HW) * C;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int i = tid + 256 * k, r = i >> 3, q = i & 7;
-            const bool ok = hw0 + r < HW && c0 + 8 * q < C;
-            load8<TT>(tb + (ok ? (size_t)(hw0 + r) * C + c0 + 8 * q : 0), v[k]);
-        }
-    }
-    __device__ __forceinline__ void store(float (&tile)[64][65], int C, int HW, int hw0, int c0) const {
-        const int tid = threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int i = tid + 256 * k, r = i >> 3, q = i & 7;
-            const bool ok = hw0 + r < HW && c0 + 8 * q < C;  // (masked here, not at the load: no wait per load)
-#pragma unroll
-            for (int j = 0; j < 8; j++) tile[r][8 * q + j] = ok ? v[k][j] : 0.f;
-        }
-    }
-};
-template <class TI, class TT>
-__global__ __launch_bounds__(256) void k_mva_gn_part_v(int F, int C, int HW, const TI *__restrict__ x,
-                                                       const TT *__restrict__ dtok, float2 *__restrict__ part) {
-    __shared__ float tile[64][65];  // dy [pixel][channel]
-    __shared__ float xs[64][65];    // x [channel][pixel]
-    __shared__ float2 red[4][64];
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    const int nT = gridDim.x;
-    {
-        float xv[4][4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {  // x along hw (zero outside)
-            const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-            const bool ok = c0 + r < C && hw0 + 4 * p < HW;
-            load4<TI>(x + (ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p : 0), xv[k]);
-        }
-        TokTileV<TT> tt;
-        tt.load(dtok, F, C, HW, bf, hw0, c0);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-            const bool ok = c0 + r < C && hw0 + 4 * p < HW;
-#pragma unroll
-            for (int e = 0; e < 4; e++) xs[r][4 * p + e] = ok ? xv[k][e] : 0.f;
-        }
-        tt.store(tile, C, HW, hw0, c0);
-    }
-    __syncthreads();
-    const int c = tid & 63, q = tid >> 6;  // as k_mva_gn_part
-    float sdx = 0.f, sd = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int h = 16 * q + k;
-        const float g = tile[h][c];
-        sd += g;
-        sdx = fmaf(g, xs[c][h], sdx);
-    }
-    red[q][c] = make_float2(sdx, sd);
-    __syncthreads();
-    if (tid < 64 && c0 + tid < C) {
-        const float2 a = red[0][tid], b2 = red[1][tid], c2 = red[2][tid], d2 = red[3][tid];
-        part[((size_t)bf * C + c0 + tid) * nT + blockIdx.x] =
-            make_float2((a.x + b2.x) + (c2.x + d2.x), (a.y + b2.y) + (c2.y + d2.y));
-    }
-}
-template <class TI, class TT, class TR>
-__global__ __launch_bounds__(256) void k_mva_gn_dx_v(int F, int C, int HW, int G, const TI *__restrict__ x,
-                                                     const TT *__restrict__ dtok, const TR *__restrict__ dres,
-                                                     const float *__restrict__ gamma, const float *__restrict__ rstd,
-                                                     const float2 *__restrict__ coef, TI *__restrict__ dx) {
-    __shared__ float tile[64][65];  // [pixel][channel]
-    __shared__ float sa[64], sb[64], sc[64];
-    const int hw0 = blockIdx.x * 64, c0 = blockIdx.y * 64, bf = blockIdx.z, tid = threadIdx.x;
-    const int Cg = C / G;
-    TokTileV<TT> tt;
-    tt.load(dtok, F, C, HW, bf, hw0, c0);
-    float xv[4][4], rv[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {  // x and the residual's gradient along hw
-        const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-        const bool ok = c0 + r < C && hw0 + 4 * p < HW;
-        const size_t o = ok ? ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p : 0;
-        load4<TI>(x + o, xv[k]);
-        if (dres) load4<TR>(dres + o, rv[k]);
-        else
-#pragma unroll
-            for (int e = 0; e < 4; e++) rv[k][e] = 0.f;
-    }
-    if (tid < 64 && c0 + tid < C) {
-        const int c = c0 + tid, g = c / Cg;
-        const float2 kk = coef[(size_t)bf * G + g];
-        sa[tid] = rstd[(size_t)bf * G + g] * (gamma ? gamma[c] : 1.f);
-        sb[tid] = kk.x;
-        sc[tid] = kk.y;
-    }
-    tt.store(tile, C, HW, hw0, c0);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int i = tid + 256 * k, r = i >> 4, p = i & 15;
-        if (c0 + r < C && hw0 + 4 * p < HW) {
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                o[e] = fmaf(sa[r], tile[4 * p + e][r], fmaf(sb[r], xv[k][e], sc[r])) + rv[k][e];
-            store4<TI>(dx + ((size_t)bf * C + c0 + r) * HW + hw0 + 4 * p, o);
-        }
-    }
-}
-__host__ __forceinline__ bool mva_vec_ok(int C, int HW, std::initializer_list<const void *> ps) {
+// ---- host side
+// the one predicate of the vector forms: rows of whole accesses, every tensor 16-B aligned (null: not used)
+bool mva_vec_ok(int C, int HW, std::initializer_list<const void *> ps) {
     if (C % 8 || HW % 4) return false;
     for (const void *p : ps)
         if (reinterpret_cast<uintptr_t>(p) & 15) return false;
     return true;
+}
+template <class Fn>
+int with_vec(bool vec, Fn &&fn) {  // fn(std::bool_constant<vec>{})
+    return vec ? fn(std::true_type{}) : fn(std::false_type{});
 }
 
 template <class TI, class TO>
@@ -911,69 +682,6 @@ int launch_norm(int B, int F, int C, int HW, int G, float eps, const void *x, co
     return LGM_OK;
 }
 
-template <class TY, class TR, class TO>
-int launch_out(int B, int F, int C, int HW, const void *y, const void *res, float skip, void *out, hipStream_t st) {
-    const dim3 grid((HW + 63) / 64, (C + 63) / 64, B * F);
-    const bool vec = C % 8 == 0 && HW % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) |
-                     reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    if (vec) {
-        LGM_LAUNCH("k_mva_out", st, (k_mva_out_v<TY, TR, TO><<<grid, 256, 0, st>>>(F, C, HW, (const TY *)y,
-                                                                                  (const TR *)res, skip, (TO *)out)));
-        return LGM_OK;
-    }
-    LGM_LAUNCH("k_mva_out", st,
-               (k_mva_out<TY, TR, TO><<<grid, 256, 0, st>>>(F, C, HW, (const TY *)y, (const TR *)res, skip, (TO *)out)));
-    return LGM_OK;
-}
-
-template <class TI>
-int norm_by_out(int dto, int B, int F, int C, int HW, int G, float eps, const void *x, const float *gamma,
-                const float *beta, void *tok, float *mean, float *rstd, float2 *part, hipStream_t st) {
-    switch (dto) {
-        case LGM_ATTN_F32: return launch_norm<TI, float>(B, F, C, HW, G, eps, x, gamma, beta, tok, mean, rstd, part, st);
-        case LGM_ATTN_BF16: return launch_norm<TI, __hip_bfloat16>(B, F, C, HW, G, eps, x, gamma, beta, tok, mean, rstd, part, st);
-        case LGM_ATTN_F16: return launch_norm<TI, __half>(B, F, C, HW, G, eps, x, gamma, beta, tok, mean, rstd, part, st);
-    }
-    set_error("lgm_mva_norm_tokens: bad output dtype %d", dto);
-    return LGM_E_INVALID;
-}
-
-template <class TY, class TR>
-int out_by_o(int dto, int B, int F, int C, int HW, const void *y, const void *res, float skip, void *out,
-             hipStream_t st) {
-    switch (dto) {
-        case LGM_ATTN_F32: return launch_out<TY, TR, float>(B, F, C, HW, y, res, skip, out, st);
-        case LGM_ATTN_BF16: return launch_out<TY, TR, __hip_bfloat16>(B, F, C, HW, y, res, skip, out, st);
-        case LGM_ATTN_F16: return launch_out<TY, TR, __half>(B, F, C, HW, y, res, skip, out, st);
-    }
-    set_error("lgm_mva_tokens_out: bad output dtype %d", dto);
-    return LGM_E_INVALID;
-}
-
-template <class TY>
-int out_by_r(int dtr, int dto, int B, int F, int C, int HW, const void *y, const void *res, float skip, void *out,
-             hipStream_t st) {
-    switch (dtr) {
-        case LGM_ATTN_F32: return out_by_o<TY, float>(dto, B, F, C, HW, y, res, skip, out, st);
-        case LGM_ATTN_BF16: return out_by_o<TY, __hip_bfloat16>(dto, B, F, C, HW, y, res, skip, out, st);
-        case LGM_ATTN_F16: return out_by_o<TY, __half>(dto, B, F, C, HW, y, res, skip, out, st);
-    }
-    set_error("lgm_mva_tokens_out: bad residual dtype %d", dtr);
-    return LGM_E_INVALID;
-}
-
-// backward launchers: the dtype switches (LGM_ATTN_F32 / BF16 / F16 codes -> types)
-template <class Fn>
-int with_type(int code, Fn &&fn) {
-    switch (code) {
-        case LGM_ATTN_F32: return fn(float{});
-        case LGM_ATTN_BF16: return fn(__hip_bfloat16{});
-        case LGM_ATTN_F16: return fn(__half{});
-    }
-    set_error("lgm_mva backward: bad dtype %d", code);
-    return LGM_E_INVALID;
-}
-
 size_t gn_part_bytes(int BF, int C, int HW) { return (((size_t)BF * C * ((HW + 63) / 64) * sizeof(float2)) + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -1000,20 +708,19 @@ extern "C" int lgm_mva_tokens_out_backward(int dtype_dout, int dtype_dy, int dty
     }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((HW + 63) / 64, (C + 63) / 64, B * F);
-    return lgm::with_type(dtype_dout, [&](auto td) {
+    const char *who = "lgm_mva_tokens_out_backward";
+    return lgm::with_type(who, dtype_dout, [&](auto td) {
         using TD = decltype(td);
-        return lgm::with_type(dtype_dy, [&](auto ty) {
+        return lgm::with_type(who, dtype_dy, [&](auto ty) {
             using TY = decltype(ty);
-            return lgm::with_type(d_res ? dtype_dres : LGM_ATTN_F32, [&](auto tr) {
+            return lgm::with_type(who, d_res ? dtype_dres : LGM_ATTN_F32, [&](auto tr) {  // (no d_res: not used)
                 using TR = decltype(tr);
-                if (lgm::mva_vec_ok(C, HW, {d_out, d_y, d_res})) {
-                    LGM_LAUNCH("k_mva_out_bwd", st, (lgm::k_mva_out_bwd_v<TD, TY, TR><<<grid, 256, 0, st>>>(
-                                                         F, C, HW, (const TD *)d_out, scale, (TY *)d_y, (TR *)d_res)));
+                return lgm::with_vec(lgm::mva_vec_ok(C, HW, {d_out, d_y, d_res}), [&](auto vec) {
+                    LGM_LAUNCH("k_mva_out_bwd", st,
+                               (lgm::k_mva_out_bwd<TD, TY, TR, decltype(vec)::value><<<grid, 256, 0, st>>>(
+                                   F, C, HW, (const TD *)d_out, scale, (TY *)d_y, (TR *)d_res)));
                     return LGM_OK;
-                }
-                LGM_LAUNCH("k_mva_out_bwd", st, (lgm::k_mva_out_bwd<TD, TY, TR><<<grid, 256, 0, st>>>(
-                                                     F, C, HW, (const TD *)d_out, scale, (TY *)d_y, (TR *)d_res)));
-                return LGM_OK;
+                });
             });
         });
     });
@@ -1045,28 +752,24 @@ extern "C" int lgm_mva_norm_tokens_backward(int dtype_x, int dtype_tok, int B, i
     float2 *part = (float2 *)workspace;
     float2 *coef = (float2 *)((char *)workspace + lgm::gn_part_bytes(BF, C, HW));
     const dim3 grid(nT, (C + 63) / 64, BF);
-    return lgm::with_type(dtype_x, [&](auto tx) {
+    const char *who = "lgm_mva_norm_tokens_backward";
+    return lgm::with_type(who, dtype_x, [&](auto tx) {
         using TI = decltype(tx);
-        return lgm::with_type(dtype_tok, [&](auto tt) {
+        return lgm::with_type(who, dtype_tok, [&](auto tt) {
             using TT = decltype(tt);
-            const bool vec = lgm::mva_vec_ok(C, HW, {x, d_tokens, d_res, dx});
-            if (vec)
-                LGM_LAUNCH("k_mva_gn_part", st, (lgm::k_mva_gn_part_v<TI, TT><<<grid, 256, 0, st>>>(
+            return lgm::with_vec(lgm::mva_vec_ok(C, HW, {x, d_tokens, d_res, dx}), [&](auto vec) {
+                constexpr bool VEC = decltype(vec)::value;
+                LGM_LAUNCH("k_mva_gn_part", st, (lgm::k_mva_gn_part<TI, TT, VEC><<<grid, 256, 0, st>>>(
                                                      F, C, HW, (const TI *)x, (const TT *)d_tokens, part)));
-            else
-                LGM_LAUNCH("k_mva_gn_part", st, (lgm::k_mva_gn_part<TI, TT><<<grid, 256, 0, st>>>(
-                                                     F, C, HW, (const TI *)x, (const TT *)d_tokens, part)));
-            LGM_LAUNCH("k_mva_gn_coef", st, (lgm::k_mva_gn_coef<<<groups, 256, 0, st>>>(
-                                                 BF, C, HW, groups, nT, part, gamma, mean, rstd, coef, dgamma, dbeta)));
-            if (dx && vec)
-                LGM_LAUNCH("k_mva_gn_dx", st, (lgm::k_mva_gn_dx_v<TI, TT, TI><<<grid, 256, 0, st>>>(
-                                                   F, C, HW, groups, (const TI *)x, (const TT *)d_tokens,
-                                                   (const TI *)d_res, gamma, rstd, coef, (TI *)dx)));
-            else if (dx)
-                LGM_LAUNCH("k_mva_gn_dx", st, (lgm::k_mva_gn_dx<TI, TT, TI><<<grid, 256, 0, st>>>(
-                                                   F, C, HW, groups, (const TI *)x, (const TT *)d_tokens,
-                                                   (const TI *)d_res, gamma, rstd, coef, (TI *)dx)));
-            return LGM_OK;
+                LGM_LAUNCH("k_mva_gn_coef", st,
+                           (lgm::k_mva_gn_coef<<<groups, 256, 0, st>>>(BF, C, HW, groups, nT, part, gamma, mean, rstd,
+                                                                       coef, dgamma, dbeta)));
+                if (dx)
+                    LGM_LAUNCH("k_mva_gn_dx", st, (lgm::k_mva_gn_dx<TI, TT, TI, VEC><<<grid, 256, 0, st>>>(
+                                                       F, C, HW, groups, (const TI *)x, (const TT *)d_tokens,
+                                                       (const TI *)d_res, gamma, rstd, coef, (TI *)dx)));
+                return LGM_OK;
+            });
         });
     });
 }
@@ -1098,17 +801,13 @@ extern "C" int lgm_mva_norm_tokens(int dtype_x, int dtype_tok, int B, int F, int
     }
     float2 *part = (float2 *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype_x) {
-        case LGM_ATTN_F32:
-            return lgm::norm_by_out<float>(dtype_tok, B, F, C, HW, groups, eps, x, gamma, beta, tokens, mean, rstd, part, st);
-        case LGM_ATTN_BF16:
-            return lgm::norm_by_out<__hip_bfloat16>(dtype_tok, B, F, C, HW, groups, eps, x, gamma, beta, tokens, mean,
-                                                    rstd, part, st);
-        case LGM_ATTN_F16:
-            return lgm::norm_by_out<__half>(dtype_tok, B, F, C, HW, groups, eps, x, gamma, beta, tokens, mean, rstd, part, st);
-    }
-    lgm::set_error("lgm_mva_norm_tokens: bad input dtype %d", dtype_x);
-    return LGM_E_INVALID;
+    const char *who = "lgm_mva_norm_tokens";
+    return lgm::with_type(who, dtype_x, [&](auto tx) {
+        return lgm::with_type(who, dtype_tok, [&](auto tt) {
+            return lgm::launch_norm<decltype(tx), decltype(tt)>(B, F, C, HW, groups, eps, x, gamma, beta, tokens, mean,
+                                                                rstd, part, st);
+        });
+    });
 }
 
 extern "C" int lgm_mva_tokens_out(int dtype_y, int dtype_res, int dtype_out, int B, int F, int C, int HW,
@@ -1126,12 +825,20 @@ extern "C" int lgm_mva_tokens_out(int dtype_y, int dtype_res, int dtype_out, int
         return LGM_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int dr = res ? dtype_res : LGM_ATTN_F32;  // (no residual: the type is not used)
-    switch (dtype_y) {
-        case LGM_ATTN_F32: return lgm::out_by_r<float>(dr, dtype_out, B, F, C, HW, y, res, skip, out, st);
-        case LGM_ATTN_BF16: return lgm::out_by_r<__hip_bfloat16>(dr, dtype_out, B, F, C, HW, y, res, skip, out, st);
-        case LGM_ATTN_F16: return lgm::out_by_r<__half>(dr, dtype_out, B, F, C, HW, y, res, skip, out, st);
-    }
-    lgm::set_error("lgm_mva_tokens_out: bad y dtype %d", dtype_y);
-    return LGM_E_INVALID;
+    const dim3 grid((HW + 63) / 64, (C + 63) / 64, B * F);
+    const char *who = "lgm_mva_tokens_out";
+    return lgm::with_type(who, dtype_y, [&](auto ty) {
+        using TY = decltype(ty);
+        return lgm::with_type(who, res ? dtype_res : LGM_ATTN_F32, [&](auto tr) {  // (no residual: not used)
+            using TR = decltype(tr);
+            return lgm::with_type(who, dtype_out, [&](auto to) {
+                using TO = decltype(to);
+                return lgm::with_vec(lgm::mva_vec_ok(C, HW, {y, res, out}), [&](auto vec) {
+                    LGM_LAUNCH("k_mva_out", st, (lgm::k_mva_out<TY, TR, TO, decltype(vec)::value><<<grid, 256, 0, st>>>(
+                                                    F, C, HW, (const TY *)y, (const TR *)res, skip, (TO *)out)));
+                    return LGM_OK;
+                });
+            });
+        });
+    });
 }
