@@ -73,6 +73,13 @@ SIGNATURES = {
     "lgm_gn_silu_backward_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "lgm_gn_silu_backward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp, _vp]),
+    "lgm_lpips_dist_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
+    "lgm_lpips_dist_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _c_size, _vp, _vp]),
+    "lgm_lpips_dist_backward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgm_lpips_prep_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgm_lpips_prep_backward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
     "lgm_profiler_create": (_vp, []),
     "lgm_profiler_summary": (_c_int, [_vp, ctypes.c_char_p, _c_size]),
     "lgm_profiler_reset": (_c_int, [_vp]),
@@ -82,7 +89,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN

@@ -2,11 +2,15 @@
 MVAttention on the HIP attention kernels), the fused Gaussian head, and the GaussianRenderer with the MSE terms
 computed inside the render kernels. Same submodule names (`unet`, `conv`), so reference checkpoints load unchanged.
 
-LPIPS: the reference builds kiui's LPIPS(net='vgg') from downloaded weights. Here the perceptual network is supplied
-by the caller -- LGM(opt, lpips=fn) with fn(gt, pred) -> per-image distances on [-1, 1] images -- and
-opt.lambda_lpips > 0 without one is an error at construction.
+LPIPS: the reference builds kiui's LPIPS(net='vgg') from downloaded weights. Here the weights come from the caller:
+LGM(opt, lpips=...) takes a state_dict or a path to one (the native lgm_amd.lpips.LPIPS is built from it), an
+lgm_amd.lpips.LPIPS, or any fn(gt, pred) -> per-image distances on [-1, 1] images; opt.lambda_lpips > 0 with nothing
+passed is an error at construction. With the native module the loss term runs on its fused input and distance kernels
+(LPIPS.loss_from_render); any other callable gets the reference's own lines.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -15,6 +19,7 @@ import torch.nn.functional as F
 from .cameras import default_rays
 from .gs import GaussianRenderer
 from .head import gaussian_head
+from .lpips import LPIPS
 from .options import Options
 from .unet import UNet
 
@@ -30,9 +35,11 @@ class LGM(nn.Module):
         self.gs = GaussianRenderer(opt)
         if opt.lambda_lpips > 0:
             if lpips is None:
-                raise ValueError("opt.lambda_lpips > 0 needs a perceptual network: pass LGM(opt, lpips=fn) with "
-                                 "fn(gt, pred) -> distances (LPIPS weights are not part of this package), or set "
-                                 "lambda_lpips = 0")
+                raise ValueError("opt.lambda_lpips > 0 needs a perceptual network: pass LGM(opt, lpips=...) with LPIPS "
+                                 "weights (a state_dict or a path: they are not part of this package), an "
+                                 "lgm_amd.lpips.LPIPS, or fn(gt, pred) -> distances; or set lambda_lpips = 0")
+            if isinstance(lpips, (str, os.PathLike, dict)):
+                lpips = LPIPS(weights=lpips)
             self.lpips_loss = lpips
             if isinstance(lpips, nn.Module):
                 lpips.requires_grad_(False)
@@ -69,12 +76,15 @@ class LGM(nn.Module):
         results = {"gaussians": gaussians, "images_pred": out["image"], "alphas_pred": out["alpha"]}
         loss = out["loss_mse"]
         if self.opt.lambda_lpips > 0:
-            S = self.opt.output_size
-            gt = gt_images * gt_masks + bg_color.view(1, 1, 3, 1, 1) * (1 - gt_masks)
-            loss_lpips = self.lpips_loss(
-                F.interpolate(gt.reshape(-1, 3, S, S) * 2 - 1, (256, 256), mode="bilinear", align_corners=False),
-                F.interpolate(out["image"].reshape(-1, 3, S, S) * 2 - 1, (256, 256), mode="bilinear",
-                              align_corners=False)).mean()
+            if isinstance(self.lpips_loss, LPIPS):  # composite, resize and distances on the fused kernels
+                loss_lpips = self.lpips_loss.loss_from_render(gt_images, gt_masks, bg_color, out["image"]).mean()
+            else:
+                S = self.opt.output_size
+                gt = gt_images * gt_masks + bg_color.view(1, 1, 3, 1, 1) * (1 - gt_masks)
+                loss_lpips = self.lpips_loss(
+                    F.interpolate(gt.reshape(-1, 3, S, S) * 2 - 1, (256, 256), mode="bilinear", align_corners=False),
+                    F.interpolate(out["image"].reshape(-1, 3, S, S) * 2 - 1, (256, 256), mode="bilinear",
+                                  align_corners=False)).mean()
             results["loss_lpips"] = loss_lpips
             loss = loss + self.opt.lambda_lpips * loss_lpips
         results["loss"] = loss

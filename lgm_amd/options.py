@@ -24,8 +24,9 @@ class Options:
     mid_attention: bool = True
     up_channels: Tuple[int, ...] = (1024, 1024, 512, 256)
     up_attention: Tuple[bool, ...] = (True, True, True, False)
-    # LPIPS weight of the loss. The reference defaults to 1.0 with downloaded VGG weights; here the LPIPS network is
-    # supplied by the caller (lgm_amd.models.LGM(opt, lpips=...)), so the default is off.
+    # LPIPS weight of the loss. The reference defaults to 1.0 with downloaded VGG weights; here the weights (for the
+    # native lgm_amd.lpips.LPIPS) or a network are supplied by the caller (lgm_amd.models.LGM(opt, lpips=...)), so the
+    # default is off.
     lambda_lpips: float = 0.0
 
 
