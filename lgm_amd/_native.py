@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("LGM_AMD_LIB") or os.path.join(os.path.dirname(os.path
                                                           "liblgm_amd.so")
 
 _c_int, _c_ll, _c_float, _c_size, _vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
+_c_double = ctypes.c_double
 
 SIGNATURES = {
     "lgm_abi_version": (_c_int, []),
@@ -80,6 +81,10 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgm_lpips_prep_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgm_lpips_prep_backward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "lgm_data_cameras": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _c_double, _c_double, _c_double, _c_double,
+                                  _c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgm_data_views": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
+                                _vp, _c_double, _vp, _vp, _vp, _vp, _vp]),
     "lgm_profiler_create": (_vp, []),
     "lgm_profiler_summary": (_c_int, [_vp, ctypes.c_char_p, _c_size]),
     "lgm_profiler_reset": (_c_int, [_vp]),
@@ -94,6 +99,7 @@ RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN
 RENDER_DETERMINISTIC = 16  # include/lgm_render.h LGM_RENDER_DETERMINISTIC
+DATA_U8 = 3  # include/lgm_data.h LGM_DATA_U8
 
 
 class NativeError(RuntimeError):

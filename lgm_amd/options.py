@@ -28,6 +28,9 @@ class Options:
     # native lgm_amd.lpips.LPIPS) or a network are supplied by the caller (lgm_amd.models.LGM(opt, lpips=...)), so the
     # default is off.
     lambda_lpips: float = 0.0
+    # augmentation probabilities of the provider (core/options.py:62-64), read by lgm_amd.data.build_batch
+    prob_grid_distortion: float = 0.5
+    prob_cam_jitter: float = 0.5
 
 
 _PRESETS = {
