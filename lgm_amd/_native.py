@@ -85,6 +85,11 @@ SIGNATURES = {
                                   _c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgm_data_views": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
                                 _vp, _c_double, _vp, _vp, _vp, _vp, _vp]),
+    "lgm_optim_workspace_size": (_c_size, [_c_ll]),
+    "lgm_optim_grad_norm": (_c_int, [_vp, _c_int, _vp, _c_ll, _c_double, _vp, _c_size, _vp, _vp, _vp]),
+    "lgm_optim_adamw": (_c_int, [_vp, _c_int, _vp, _c_ll, _c_ll, _vp, _c_double, _c_double, _c_double, _c_double,
+                                 _c_double, _c_double, _vp, _vp]),
+    "lgm_optim_scale": (_c_int, [_vp, _c_int, _vp, _c_ll, _vp, _vp, _vp]),
     "lgm_profiler_create": (_vp, []),
     "lgm_profiler_summary": (_c_int, [_vp, ctypes.c_char_p, _c_size]),
     "lgm_profiler_reset": (_c_int, [_vp]),
@@ -94,12 +99,13 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN
 RENDER_DETERMINISTIC = 16  # include/lgm_render.h LGM_RENDER_DETERMINISTIC
 DATA_U8 = 3  # include/lgm_data.h LGM_DATA_U8
+OPTIM_CHUNK = 4096  # include/lgm_optim.h LGM_OPTIM_CHUNK
 
 
 class NativeError(RuntimeError):
