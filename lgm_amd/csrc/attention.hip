@@ -6,16 +6,27 @@
 // q/k/v are read in place from the packed qkv Linear output [B, L, 3, H, D] (row stride ld = 3 H D elements), so
 // the reshape/unbind of core/attention.py:75-77 costs nothing; dq/dk/dv are written back packed the same way.
 //
-// Design (CDNA4, wave64, 16x16 MFMA tiles; fp32 accumulation):
+// Common to both paths (CDNA4, wave64, 16x16 MFMA tiles; fp32 accumulation):
 //   * scores are computed TRANSPOSED, S^T = K Q^T, so every lane owns one query column (q = lane & 15) and holds
 //     4 keys of each 16-key sub-tile: the online-softmax row state (m, l) and the O^T accumulator live in the
-//     same lane, and the P tile feeds the P V product from registers (its key order permuted to match the
-//     accumulator layout; the matching V^T operand is read with the same permutation from LDS);
-//   * bf16 / fp16 use v_mfma_f32_16x16x32_{bf16,f16}; fp32 uses the exact-f32 v_mfma_f32_16x16x4_f32, so fp32
-//     inputs keep the fp32 accuracy of the reference's fallback;
+//     same lane, and the P tile feeds the P V product from registers;
 //   * the softmax runs in base 2 (exp2 with a log2(e) prescale); LSE is stored in natural log for the backward;
-//   * backward = delta = rowsum(dO * O), then a dQ kernel (per query block, loops over key blocks) and a dK/dV
-//     kernel (per key block, loops over query blocks): no atomics, deterministic.
+//   * the backward has a dQ kernel (per query block, loops over key blocks) and a dK/dV kernel (per key block,
+//     loops over query blocks): no atomics, deterministic.
+//
+// Two paths, chosen by the element type. The profiler labels ("k_attn_fwd", ...) are the same on both.
+//   fp32 (exact-f32 v_mfma_f32_16x16x4_f32: fp32 inputs keep the fp32 accuracy of the reference's fallback):
+//     forward   k_attn_fwd<D>
+//     backward  k_attn_delta<D> (delta = rowsum(dO * O) into the workspace), then k_attn_dq<D>, then
+//               k_attn_dkdv<D>; both read delta and lse.
+//   bf16 / fp16 (v_mfma_f32_16x16x32_{bf16,f16}, LDS-DMA or register-staged double-buffered tiles, transposed
+//   operands by ds_read_b64_tr_b16):
+//     forward   k_attn_fwd2<DT, D, QS>, QS = 1, 2 or 4 query sub-tiles per wavefront by grid size (fwd_16)
+//     backward  k_attn_dq2<DT, D, QS>, then k_attn_dkdv2<DT, D, KS>: no delta pass. k_attn_dq2 computes delta
+//               of its own rows and writes the row constants (-lse * log2(e), -delta) and the rounded
+//               Q * scale * log2(e) to the workspace; k_attn_dkdv2 reads both from there.
+//
+// File order: shared types and fragments | fp32 path | 16-bit path | workspace layout, check, entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +39,8 @@
 namespace lgm {
 namespace attn {
 
+// ------------------------------------------------------------------------------------------------------------
+// shared types and fragments
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -37,20 +50,13 @@ constexpr float LN2 = 0.6931471805599453f;
 constexpr int BQ = 64, BK = 64, NT = 256;  // 4 wavefronts x 16 rows
 
 template <int DT> struct Ty;
-template <> struct Ty<LGM_ATTN_F32> { using T = float; static constexpr int PAD = 2; };
-template <> struct Ty<LGM_ATTN_BF16> { using T = __bf16; using V8 = bf16x8; static constexpr int PAD = 8; };
-template <> struct Ty<LGM_ATTN_F16> { using T = _Float16; using V8 = f16x8; static constexpr int PAD = 8; };
-constexpr int PADT = 4;  // transposed bf16/fp16 tiles: [D][64 + 4]
+template <> struct Ty<LGM_ATTN_F32> { using T = float; };
+template <> struct Ty<LGM_ATTN_BF16> { using T = __bf16; using V8 = bf16x8; };
+template <> struct Ty<LGM_ATTN_F16> { using T = _Float16; using V8 = f16x8; };
 
-template <typename T> __device__ __forceinline__ float to_f(T x) { return (float)x; }
 template <typename T> __device__ __forceinline__ T from_f(float x) { return (T)x; }
 
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-template <int DT> __device__ __forceinline__ f32x4 mfma32(typename Ty<DT>::V8 a, typename Ty<DT>::V8 b, f32x4 c) {
-    if constexpr (DT == LGM_ATTN_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 // Register fragment of a 16-row operand Y[row = lane & 15][0..D): fp32 -> D/4 values Y[r][4s + g];
 // 16-bit -> D/32 vectors Y[r][32c + 8g + 0..7].
@@ -77,89 +83,47 @@ __device__ __forceinline__ void load_yfrag(YFrag<DT, D> &f, const typename Ty<DT
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// fp32 path: k_attn_fwd | k_attn_delta, k_attn_dq, k_attn_dkdv on single-buffered row-major LDS tiles.
+constexpr int F32_PAD = 2;  // LDS row stride D + 2 floats
+template <int D> using FragF = YFrag<LGM_ATTN_F32, D>;
+
 // acc[i] += (X Y^T)[rb + 4g + i][lane & 15]: X rows from an LDS row-major tile (stride ldx), Y = register frag.
-template <int DT, int D>
-__device__ __forceinline__ void s_like(f32x4 &acc, const typename Ty<DT>::T *X, int ldx, int rb,
-                                       const YFrag<DT, D> &y, int g, int r16) {
-    const typename Ty<DT>::T *xr = X + (rb + r16) * ldx;
-    if constexpr (DT == LGM_ATTN_F32) {
+template <int D>
+__device__ __forceinline__ void s_like(f32x4 &acc, const float *X, int ldx, int rb, const FragF<D> &y, int g,
+                                       int r16) {
+    const float *xr = X + (rb + r16) * ldx;
 #pragma unroll
-        for (int s = 0; s < D / 4; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xr[4 * s + g], y.v[s], acc, 0, 0, 0);
-    } else {
-        using V8 = typename Ty<DT>::V8;
-#pragma unroll
-        for (int c = 0; c < D / 32; c++)
-            acc = mfma32<DT>(*reinterpret_cast<const V8 *>(xr + 32 * c + 8 * g), y.v[c], acc);
-    }
+    for (int s = 0; s < D / 4; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xr[4 * s + g], y.v[s], acc, 0, 0, 0);
 }
 
 // acc[dt][i] += (Z^T P)[d = 16 dt + 4g + i][col = lane & 15] over the 64 keys of a block, where P is held by the
-// lanes as own[sub][i] = P[key = 16 sub + 4g + i][col]. fp32: Z is the row-major LDS tile [key][d] (stride ldz);
-// 16-bit: Zt is the TRANSPOSED LDS tile [d][key] (stride ldzt), read with the key permutation of the operand.
-template <int DT, int D>
-__device__ __forceinline__ void pv_like(f32x4 (&acc)[D / 16], const typename Ty<DT>::T *Z, int ldz,
-                                        const float (&own)[4][4], int g, int r16) {
-    if constexpr (DT == LGM_ATTN_F32) {
+// lanes as own[sub][i] = P[key = 16 sub + 4g + i][col] and Z is the row-major LDS tile [key][d] (stride ldz).
+template <int D>
+__device__ __forceinline__ void pv_like(f32x4 (&acc)[D / 16], const float *Z, int ldz, const float (&own)[4][4], int g,
+                                        int r16) {
 #pragma unroll
-        for (int dt = 0; dt < D / 16; dt++)
+    for (int dt = 0; dt < D / 16; dt++)
 #pragma unroll
-            for (int sub = 0; sub < 4; sub++)
+        for (int sub = 0; sub < 4; sub++)
 #pragma unroll
-                for (int i = 0; i < 4; i++)
-                    acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Z[(16 * sub + 4 * g + i) * ldz + 16 * dt + r16],
-                                                                    own[sub][i], acc[dt], 0, 0, 0);
-    } else {
-        using T = typename Ty<DT>::T;
-        using V8 = typename Ty<DT>::V8;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            V8 b;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                b[i] = (T)own[2 * t][i];
-                b[4 + i] = (T)own[2 * t + 1][i];
-            }
-#pragma unroll
-            for (int dt = 0; dt < D / 16; dt++) {
-                const T *zr = Z + (16 * dt + r16) * ldz + 32 * t + 4 * g;
-                const uint2 lo = *reinterpret_cast<const uint2 *>(zr);
-                const uint2 hi = *reinterpret_cast<const uint2 *>(zr + 16);
-                V8 a;
-                const uint4 packed = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                a = *reinterpret_cast<const V8 *>(&packed);
-                acc[dt] = mfma32<DT>(a, b, acc[dt]);
-            }
-        }
-    }
+            for (int i = 0; i < 4; i++)
+                acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Z[(16 * sub + 4 * g + i) * ldz + 16 * dt + r16],
+                                                                own[sub][i], acc[dt], 0, 0, 0);
 }
 
-// Cooperative loads of a 64-row block (rows r0.., tokens >= L zero-filled) from a [tokens][ld] tensor.
-template <typename T, int D, int PAD>
-__device__ __forceinline__ void load_rows(T *dst, const T *src, long long ld, int r0, int L) {
-    constexpr int VEC = 16 / sizeof(T), CPR = D / VEC;
+// Cooperative load of a 64-row block (rows r0.., tokens >= L zero-filled) from a [tokens][ld] tensor into a
+// [64][D + F32_PAD] tile: 16-B global loads, scalar LDS stores (the padded rows are 8-B aligned only).
+template <int D>
+__device__ __forceinline__ void load_rows(float *dst, const float *src, long long ld, int r0, int L) {
+    constexpr int VEC = 4, CPR = D / VEC;
     for (int c = threadIdx.x; c < 64 * CPR; c += NT) {
         const int r = c / CPR, col = (c - r * CPR) * VEC;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (r0 + r < L) v = *reinterpret_cast<const uint4 *>(src + (long long)(r0 + r) * ld + col);
-        if constexpr (PAD % VEC == 0) {
-            *reinterpret_cast<uint4 *>(dst + r * (D + PAD) + col) = v;
-        } else {
-            const T *pv = reinterpret_cast<const T *>(&v);
+        const float *pv = reinterpret_cast<const float *>(&v);
 #pragma unroll
-            for (int j = 0; j < VEC; j++) dst[r * (D + PAD) + col + j] = pv[j];
-        }
-    }
-}
-template <typename T, int D>
-__device__ __forceinline__ void load_rows_T(T *dst, const T *src, long long ld, int r0, int L) {
-    constexpr int VEC = 16 / sizeof(T), CPR = D / VEC;
-    for (int c = threadIdx.x; c < 64 * CPR; c += NT) {
-        const int r = c / CPR, col = (c - r * CPR) * VEC;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (r0 + r < L) v = *reinterpret_cast<const uint4 *>(src + (long long)(r0 + r) * ld + col);
-        const T *pv = reinterpret_cast<const T *>(&v);
-#pragma unroll
-        for (int j = 0; j < VEC; j++) dst[(col + j) * (64 + PADT) + r] = pv[j];
+        for (int j = 0; j < VEC; j++) dst[r * (D + F32_PAD) + col + j] = pv[j];
     }
 }
 
@@ -172,42 +136,37 @@ __device__ __forceinline__ float xsum4(float v) {
     return v + __shfl_xor(v, 32, 64);
 }
 
-// ------------------------------------------------------------------------------------------------------------
 // forward: grid (ceil(L/64), B*H), block 256.
-template <int DT, int D>
-__global__ __launch_bounds__(NT) void k_attn_fwd(int L, int H, float scale, const typename Ty<DT>::T *__restrict__ q,
-                                                 const typename Ty<DT>::T *__restrict__ k,
-                                                 const typename Ty<DT>::T *__restrict__ v, long long ld,
-                                                 typename Ty<DT>::T *__restrict__ o, float *__restrict__ lse) {
-    using T = typename Ty<DT>::T;
-    constexpr int PAD = Ty<DT>::PAD;
-    constexpr bool F32 = DT == LGM_ATTN_F32;
-    __shared__ __attribute__((aligned(16))) T Ks[64 * (D + PAD)];
-    __shared__ __attribute__((aligned(16))) T Vs[F32 ? 64 * (D + PAD) : D * (64 + PADT)];
+template <int D>
+__global__ __launch_bounds__(NT) void k_attn_fwd(int L, int H, float scale, const float *__restrict__ q,
+                                                 const float *__restrict__ k, const float *__restrict__ v,
+                                                 long long ld, float *__restrict__ o, float *__restrict__ lse) {
+    constexpr int LDT = D + F32_PAD;
+    __shared__ __attribute__((aligned(16))) float Ks[64 * LDT];
+    __shared__ __attribute__((aligned(16))) float Vs[64 * LDT];
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
     const long long base = (long long)b * L * ld + (long long)h * D;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, g = lane >> 4, r16 = lane & 15;
     const int qrow = blockIdx.x * BQ + w * 16 + r16;
     const bool qvalid = qrow < L;
     const float c = scale * LOG2E;
-    YFrag<DT, D> qf;
-    load_yfrag<DT, D>(qf, q + base + (long long)qrow * ld, qvalid, g);
+    FragF<D> qf;
+    load_yfrag<LGM_ATTN_F32, D>(qf, q + base + (long long)qrow * ld, qvalid, g);
     f32x4 oacc[D / 16];
 #pragma unroll
     for (int dt = 0; dt < D / 16; dt++) oacc[dt] = zero4();
     float m = -INFINITY, lsum = 0.f;
     for (int kb = 0; kb < L; kb += BK) {
         __syncthreads();
-        load_rows<T, D, PAD>(Ks, k + base, ld, kb, L);
-        if constexpr (F32) load_rows<T, D, PAD>(Vs, v + base, ld, kb, L);
-        else load_rows_T<T, D>(Vs, v + base, ld, kb, L);
+        load_rows<D>(Ks, k + base, ld, kb, L);
+        load_rows<D>(Vs, v + base, ld, kb, L);
         __syncthreads();
         float p[4][4];
         float mloc = -INFINITY;
 #pragma unroll
         for (int sub = 0; sub < 4; sub++) {
             f32x4 s = zero4();
-            s_like<DT, D>(s, Ks, D + PAD, 16 * sub, qf, g, r16);
+            s_like<D>(s, Ks, LDT, 16 * sub, qf, g, r16);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const float x = (kb + 16 * sub + 4 * g + i < L) ? s[i] * c : -INFINITY;
@@ -230,25 +189,24 @@ __global__ __launch_bounds__(NT) void k_attn_fwd(int L, int H, float scale, cons
         lsum = lsum * alpha + xsum4(ls);
 #pragma unroll
         for (int dt = 0; dt < D / 16; dt++) oacc[dt] *= alpha;
-        pv_like<DT, D>(oacc, Vs, F32 ? D + PAD : 64 + PADT, p, g, r16);
+        pv_like<D>(oacc, Vs, LDT, p, g, r16);
         m = mnew;
     }
     if (qvalid) {
         const float inv = 1.f / lsum;
-        T *orow = o + ((long long)b * L + qrow) * ((long long)H * D) + (long long)h * D;
+        float *orow = o + ((long long)b * L + qrow) * ((long long)H * D) + (long long)h * D;
 #pragma unroll
         for (int dt = 0; dt < D / 16; dt++)
 #pragma unroll
-            for (int i = 0; i < 4; i++) orow[16 * dt + 4 * g + i] = from_f<T>(oacc[dt][i] * inv);
+            for (int i = 0; i < 4; i++) orow[16 * dt + 4 * g + i] = oacc[dt][i] * inv;
         if (g == 0) lse[(long long)bh * L + qrow] = (m + log2f(lsum)) * LN2;
     }
 }
 
-// delta[bh][q] = sum_d dO[q][d] * O[q][d]  (fp32); grid ceil(B*L*H / 256).
-template <int DT, int D>
-__global__ __launch_bounds__(256) void k_attn_delta(int B, int L, int H, const typename Ty<DT>::T *__restrict__ o,
-                                                    const typename Ty<DT>::T *__restrict__ dout,
-                                                    float *__restrict__ delta) {
+// delta[bh][q] = sum_d dO[q][d] * O[q][d]; grid ceil(B*L*H / 256).
+template <int D>
+__global__ __launch_bounds__(256) void k_attn_delta(int B, int L, int H, const float *__restrict__ o,
+                                                    const float *__restrict__ dout, float *__restrict__ delta) {
     // thread -> (b, h, q), q fastest: the delta row is written coalesced (with h fastest every wave scattered its 64
     // floats over 16 rows of L: 25 -> ? us at 8 x 16 x 4096 rows); each thread still reads its own contiguous D-vector
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -259,24 +217,20 @@ __global__ __launch_bounds__(256) void k_attn_delta(int B, int L, int H, const t
     const long long off = (((long long)b * L + qrow) * H + h) * D;
     float s = 0.f;
 #pragma unroll 8
-    for (int d = 0; d < D; d++) s += to_f(o[off + d]) * to_f(dout[off + d]);
+    for (int d = 0; d < D; d++) s += o[off + d] * dout[off + d];
     delta[idx] = s;
 }
 
 // dQ: grid (ceil(L/64), B*H). dQ = scale * sum_k dS K with dS = P o (dP - delta), P = exp(scale S - lse).
-template <int DT, int D>
-__global__ __launch_bounds__(NT) void k_attn_dq(int L, int H, float scale, const typename Ty<DT>::T *__restrict__ q,
-                                                const typename Ty<DT>::T *__restrict__ k,
-                                                const typename Ty<DT>::T *__restrict__ v, long long ld,
-                                                const typename Ty<DT>::T *__restrict__ dout,
+template <int D>
+__global__ __launch_bounds__(NT) void k_attn_dq(int L, int H, float scale, const float *__restrict__ q,
+                                                const float *__restrict__ k, const float *__restrict__ v,
+                                                long long ld, const float *__restrict__ dout,
                                                 const float *__restrict__ lse, const float *__restrict__ delta,
-                                                typename Ty<DT>::T *__restrict__ dq, long long ldd) {
-    using T = typename Ty<DT>::T;
-    constexpr int PAD = Ty<DT>::PAD;
-    constexpr bool F32 = DT == LGM_ATTN_F32;
-    __shared__ __attribute__((aligned(16))) T Ks[64 * (D + PAD)];
-    __shared__ __attribute__((aligned(16))) T Vs[64 * (D + PAD)];
-    __shared__ __attribute__((aligned(16))) T Kt[F32 ? 1 : D * (64 + PADT)];
+                                                float *__restrict__ dq, long long ldd) {
+    constexpr int LDT = D + F32_PAD;
+    __shared__ __attribute__((aligned(16))) float Ks[64 * LDT];
+    __shared__ __attribute__((aligned(16))) float Vs[64 * LDT];
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
     const long long base = (long long)b * L * ld + (long long)h * D;
     const long long obase = (long long)b * L * H * D + (long long)h * D;
@@ -284,9 +238,9 @@ __global__ __launch_bounds__(NT) void k_attn_dq(int L, int H, float scale, const
     const int qrow = blockIdx.x * BQ + w * 16 + r16;
     const bool qvalid = qrow < L;
     const float c = scale * LOG2E;
-    YFrag<DT, D> qf, dof;
-    load_yfrag<DT, D>(qf, q + base + (long long)qrow * ld, qvalid, g);
-    load_yfrag<DT, D>(dof, dout + obase + (long long)qrow * H * D, qvalid, g);
+    FragF<D> qf, dof;
+    load_yfrag<LGM_ATTN_F32, D>(qf, q + base + (long long)qrow * ld, qvalid, g);
+    load_yfrag<LGM_ATTN_F32, D>(dof, dout + obase + (long long)qrow * H * D, qvalid, g);
     const float lse2 = qvalid ? lse[(long long)bh * L + qrow] * LOG2E : 0.f;
     const float dlt = qvalid ? delta[(long long)bh * L + qrow] : 0.f;
     f32x4 acc[D / 16];
@@ -294,16 +248,15 @@ __global__ __launch_bounds__(NT) void k_attn_dq(int L, int H, float scale, const
     for (int dt = 0; dt < D / 16; dt++) acc[dt] = zero4();
     for (int kb = 0; kb < L; kb += BK) {
         __syncthreads();
-        load_rows<T, D, PAD>(Ks, k + base, ld, kb, L);
-        load_rows<T, D, PAD>(Vs, v + base, ld, kb, L);
-        if constexpr (!F32) load_rows_T<T, D>(Kt, k + base, ld, kb, L);
+        load_rows<D>(Ks, k + base, ld, kb, L);
+        load_rows<D>(Vs, v + base, ld, kb, L);
         __syncthreads();
         float ds[4][4];
 #pragma unroll
         for (int sub = 0; sub < 4; sub++) {
             f32x4 s = zero4(), dp = zero4();
-            s_like<DT, D>(s, Ks, D + PAD, 16 * sub, qf, g, r16);
-            s_like<DT, D>(dp, Vs, D + PAD, 16 * sub, dof, g, r16);
+            s_like<D>(s, Ks, LDT, 16 * sub, qf, g, r16);
+            s_like<D>(dp, Vs, LDT, 16 * sub, dof, g, r16);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const bool kv = kb + 16 * sub + 4 * g + i < L;
@@ -311,33 +264,27 @@ __global__ __launch_bounds__(NT) void k_attn_dq(int L, int H, float scale, const
                 ds[sub][i] = p * (dp[i] - dlt);
             }
         }
-        pv_like<DT, D>(acc, F32 ? Ks : Kt, F32 ? D + PAD : 64 + PADT, ds, g, r16);
+        pv_like<D>(acc, Ks, LDT, ds, g, r16);
     }
     if (qvalid) {
-        T *row = dq + (long long)b * L * ldd + (long long)qrow * ldd + (long long)h * D;
+        float *row = dq + (long long)b * L * ldd + (long long)qrow * ldd + (long long)h * D;
 #pragma unroll
         for (int dt = 0; dt < D / 16; dt++)
 #pragma unroll
-            for (int i = 0; i < 4; i++) row[16 * dt + 4 * g + i] = from_f<T>(acc[dt][i] * scale);
+            for (int i = 0; i < 4; i++) row[16 * dt + 4 * g + i] = acc[dt][i] * scale;
     }
 }
 
 // dK, dV: grid (ceil(L/64), B*H); each wavefront owns 16 keys, loops over all query blocks.
-template <int DT, int D>
-__global__ __launch_bounds__(NT) void k_attn_dkdv(int L, int H, float scale, const typename Ty<DT>::T *__restrict__ q,
-                                                  const typename Ty<DT>::T *__restrict__ k,
-                                                  const typename Ty<DT>::T *__restrict__ v, long long ld,
-                                                  const typename Ty<DT>::T *__restrict__ dout,
+template <int D>
+__global__ __launch_bounds__(NT) void k_attn_dkdv(int L, int H, float scale, const float *__restrict__ q,
+                                                  const float *__restrict__ k, const float *__restrict__ v,
+                                                  long long ld, const float *__restrict__ dout,
                                                   const float *__restrict__ lse, const float *__restrict__ delta,
-                                                  typename Ty<DT>::T *__restrict__ dk, typename Ty<DT>::T *__restrict__ dv,
-                                                  long long ldd) {
-    using T = typename Ty<DT>::T;
-    constexpr int PAD = Ty<DT>::PAD;
-    constexpr bool F32 = DT == LGM_ATTN_F32;
-    __shared__ __attribute__((aligned(16))) T Qs[64 * (D + PAD)];
-    __shared__ __attribute__((aligned(16))) T Os[64 * (D + PAD)];  // dO rows
-    __shared__ __attribute__((aligned(16))) T Qt[F32 ? 1 : D * (64 + PADT)];
-    __shared__ __attribute__((aligned(16))) T Ot[F32 ? 1 : D * (64 + PADT)];
+                                                  float *__restrict__ dk, float *__restrict__ dv, long long ldd) {
+    constexpr int LDT = D + F32_PAD;
+    __shared__ __attribute__((aligned(16))) float Qs[64 * LDT];
+    __shared__ __attribute__((aligned(16))) float Os[64 * LDT];  // dO rows
     __shared__ float sl[64], sd[64];
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
     const long long base = (long long)b * L * ld + (long long)h * D;
@@ -346,20 +293,16 @@ __global__ __launch_bounds__(NT) void k_attn_dkdv(int L, int H, float scale, con
     const int key = blockIdx.x * BK + w * 16 + r16;
     const bool kvalid = key < L;
     const float c = scale * LOG2E;
-    YFrag<DT, D> kf, vf;
-    load_yfrag<DT, D>(kf, k + base + (long long)key * ld, kvalid, g);
-    load_yfrag<DT, D>(vf, v + base + (long long)key * ld, kvalid, g);
+    FragF<D> kf, vf;
+    load_yfrag<LGM_ATTN_F32, D>(kf, k + base + (long long)key * ld, kvalid, g);
+    load_yfrag<LGM_ATTN_F32, D>(vf, v + base + (long long)key * ld, kvalid, g);
     f32x4 dka[D / 16], dva[D / 16];
 #pragma unroll
     for (int dt = 0; dt < D / 16; dt++) { dka[dt] = zero4(); dva[dt] = zero4(); }
     for (int qb = 0; qb < L; qb += BQ) {
         __syncthreads();
-        load_rows<T, D, PAD>(Qs, q + base, ld, qb, L);
-        load_rows<T, D, PAD>(Os, dout + obase, (long long)H * D, qb, L);
-        if constexpr (!F32) {
-            load_rows_T<T, D>(Qt, q + base, ld, qb, L);
-            load_rows_T<T, D>(Ot, dout + obase, (long long)H * D, qb, L);
-        }
+        load_rows<D>(Qs, q + base, ld, qb, L);
+        load_rows<D>(Os, dout + obase, (long long)H * D, qb, L);
         if (tid < 64) {
             const bool qv = qb + tid < L;
             sl[tid] = qv ? lse[(long long)bh * L + qb + tid] * LOG2E : INFINITY;  // invalid rows: P = 0
@@ -370,8 +313,8 @@ __global__ __launch_bounds__(NT) void k_attn_dkdv(int L, int H, float scale, con
 #pragma unroll
         for (int sub = 0; sub < 4; sub++) {
             f32x4 s = zero4(), dp = zero4();
-            s_like<DT, D>(s, Qs, D + PAD, 16 * sub, kf, g, r16);   // S[q = 16 sub + 4g + i][key]
-            s_like<DT, D>(dp, Os, D + PAD, 16 * sub, vf, g, r16);  // dP[q][key]
+            s_like<D>(s, Qs, LDT, 16 * sub, kf, g, r16);   // S[q = 16 sub + 4g + i][key]
+            s_like<D>(dp, Os, LDT, 16 * sub, vf, g, r16);  // dP[q][key]
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int qi = 16 * sub + 4 * g + i;
@@ -380,24 +323,56 @@ __global__ __launch_bounds__(NT) void k_attn_dkdv(int L, int H, float scale, con
                 ds[sub][i] = e * (dp[i] - sd[qi]);
             }
         }
-        pv_like<DT, D>(dva, F32 ? Os : Ot, F32 ? D + PAD : 64 + PADT, p, g, r16);   // dV^T += dO^T P
-        pv_like<DT, D>(dka, F32 ? Qs : Qt, F32 ? D + PAD : 64 + PADT, ds, g, r16);  // dK^T += Q^T dS
+        pv_like<D>(dva, Os, LDT, p, g, r16);   // dV^T += dO^T P
+        pv_like<D>(dka, Qs, LDT, ds, g, r16);  // dK^T += Q^T dS
     }
     if (kvalid) {
-        T *krow = dk + (long long)b * L * ldd + (long long)key * ldd + (long long)h * D;
-        T *vrow = dv + (long long)b * L * ldd + (long long)key * ldd + (long long)h * D;
+        float *krow = dk + (long long)b * L * ldd + (long long)key * ldd + (long long)h * D;
+        float *vrow = dv + (long long)b * L * ldd + (long long)key * ldd + (long long)h * D;
 #pragma unroll
         for (int dt = 0; dt < D / 16; dt++)
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                krow[16 * dt + 4 * g + i] = from_f<T>(dka[dt][i] * scale);
-                vrow[16 * dt + 4 * g + i] = from_f<T>(dva[dt][i]);
+                krow[16 * dt + 4 * g + i] = dka[dt][i] * scale;
+                vrow[16 * dt + 4 * g + i] = dva[dt][i];
             }
     }
 }
 
+template <int D>
+int fwd_f32(int B, int L, int H, float scale, const void *q, const void *k, const void *v, long long ld, void *o,
+            float *lse, hipStream_t st) {
+    using CF = const float *;
+    dim3 grid((L + BQ - 1) / BQ, B * H);
+    LGM_LAUNCH("k_attn_fwd", st,
+               (k_attn_fwd<D><<<grid, NT, 0, st>>>(L, H, scale, (CF)q, (CF)k, (CF)v, ld, (float *)o, lse)));
+    return LGM_OK;
+}
+
+template <int D>
+int bwd_f32(int B, int L, int H, float scale, const void *q, const void *k, const void *v, long long ld,
+            const void *o, const float *lse, const void *dout, void *dq, void *dk, void *dv, long long ldd,
+            float *delta, hipStream_t st) {  // delta: the workspace, [B*H][L]
+    using CF = const float *;
+    const long long rows = (long long)B * L * H;
+    LGM_LAUNCH("k_attn_delta", st, (k_attn_delta<D><<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(
+                                       B, L, H, (CF)o, (CF)dout, delta)));
+    dim3 grid((L + 63) / 64, B * H);
+    LGM_LAUNCH("k_attn_dq", st, (k_attn_dq<D><<<grid, NT, 0, st>>>(L, H, scale, (CF)q, (CF)k, (CF)v, ld, (CF)dout, lse,
+                                                                 delta, (float *)dq, ldd)));
+    LGM_LAUNCH("k_attn_dkdv", st, (k_attn_dkdv<D><<<grid, NT, 0, st>>>(L, H, scale, (CF)q, (CF)k, (CF)v, ld, (CF)dout,
+                                                                     lse, delta, (float *)dk, (float *)dv, ldd)));
+    return LGM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------
-// forward, 16-bit inputs (v2): grid (ceil(L / (64 QS)), B*H), block 256; wavefront w owns 16 QS query rows.
+// 16-bit path (bf16, fp16): k_attn_fwd2 | k_attn_dq2, k_attn_dkdv2.
+template <int DT> __device__ __forceinline__ f32x4 mfma32(typename Ty<DT>::V8 a, typename Ty<DT>::V8 b, f32x4 c) {
+    if constexpr (DT == LGM_ATTN_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
+// forward (v2): grid (ceil(L / (64 QS)), B*H), block 256; wavefront w owns 16 QS query rows.
 //   * S^T = K Q^T per 16-key sub-tile: the K fragment (ds_read_b128 from the row-major tile) is read once and used
 //     for all QS query sub-tiles held in registers;
 //   * P V as O^T += V^T P: the V^T operand comes straight from the row-major V tile via ds_read_b64_tr_b16 (the
@@ -1109,79 +1084,63 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D <= 64 ? BW
 }
 
 template <int DT, int D>
-int fwd_impl(int B, int L, int H, float scale, const void *q, const void *k, const void *v, long long ld, void *o,
-             float *lse, hipStream_t st) {
+int fwd_16(int B, int L, int H, float scale, const void *q, const void *k, const void *v, long long ld, void *o,
+           float *lse, hipStream_t st) {
     using T = typename Ty<DT>::T;
-    if constexpr (DT != LGM_ATTN_F32) {
-        // two query sub-tiles per wavefront when the grid stays large enough to fill the chip; at D = 32 four (64
-        // queries per wave, 3 waves per SIMD at 168 VGPRs: each K fragment and V^T fragment read from LDS feeds four
-        // MFMAs) once the grid covers two rounds of the 768 workgroup slots: bench level (2,048 workgroups)
-        // k_attn_fwd -5 % against two, but cfg4's L = 9,600 (608 workgroups, a fifth of the slots idle) +10 %
-        // (profiles/r05/ab_attn_qs; three sub-tiles measured slower, and the same widening of dQ / dK,dV gained nothing)
-        constexpr int QS4 = D == 32 ? 4 : 0;
-        constexpr int QS2 = D <= 64 ? 2 : 1;
-        constexpr long long QS4_MIN_GRID = 1536;
-        if (QS4 && (long long)((L + 255) / 256) * B * H >= QS4_MIN_GRID) {
-            dim3 grid((L + 255) / 256, B * H);
-            LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd2<DT, D, (QS4 ? QS4 : 1)><<<grid, NT, 0, st>>>(
-                                              L, H, scale, (const T *)q, (const T *)k, (const T *)v, ld, (T *)o, lse)));
-        } else if (QS2 == 2 && (long long)((L + 127) / 128) * B * H >= QS_MIN_GRID) {
-            dim3 grid((L + 127) / 128, B * H);
-            LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd2<DT, D, QS2><<<grid, NT, 0, st>>>(
-                                              L, H, scale, (const T *)q, (const T *)k, (const T *)v, ld, (T *)o, lse)));
-        } else {
-            dim3 grid((L + 63) / 64, B * H);
-            LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd2<DT, D, 1><<<grid, NT, 0, st>>>(
-                                              L, H, scale, (const T *)q, (const T *)k, (const T *)v, ld, (T *)o, lse)));
-        }
-        return LGM_OK;
+    // two query sub-tiles per wavefront when the grid stays large enough to fill the chip; at D = 32 four (64
+    // queries per wave, 3 waves per SIMD at 168 VGPRs: each K fragment and V^T fragment read from LDS feeds four
+    // MFMAs) once the grid covers two rounds of the 768 workgroup slots: bench level (2,048 workgroups)
+    // k_attn_fwd -5 % against two, but cfg4's L = 9,600 (608 workgroups, a fifth of the slots idle) +10 %
+    // (profiles/r05/ab_attn_qs; three sub-tiles measured slower, and the same widening of dQ / dK,dV gained nothing)
+    constexpr int QS4 = D == 32 ? 4 : 0;
+    constexpr int QS2 = D <= 64 ? 2 : 1;
+    constexpr long long QS4_MIN_GRID = 1536;
+    if (QS4 && (long long)((L + 255) / 256) * B * H >= QS4_MIN_GRID) {
+        dim3 grid((L + 255) / 256, B * H);
+        LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd2<DT, D, (QS4 ? QS4 : 1)><<<grid, NT, 0, st>>>(
+                                          L, H, scale, (const T *)q, (const T *)k, (const T *)v, ld, (T *)o, lse)));
+    } else if (QS2 == 2 && (long long)((L + 127) / 128) * B * H >= QS_MIN_GRID) {
+        dim3 grid((L + 127) / 128, B * H);
+        LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd2<DT, D, QS2><<<grid, NT, 0, st>>>(
+                                          L, H, scale, (const T *)q, (const T *)k, (const T *)v, ld, (T *)o, lse)));
+    } else {
+        dim3 grid((L + 63) / 64, B * H);
+        LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd2<DT, D, 1><<<grid, NT, 0, st>>>(
+                                          L, H, scale, (const T *)q, (const T *)k, (const T *)v, ld, (T *)o, lse)));
     }
-    dim3 grid((L + BQ - 1) / BQ, B * H);
-    LGM_LAUNCH("k_attn_fwd", st, (k_attn_fwd<DT, D><<<grid, NT, 0, st>>>(L, H, scale, (const T *)q, (const T *)k,
-                                                                       (const T *)v, ld, (T *)o, lse)));
     return LGM_OK;
 }
 
+size_t qc_offset(int B, int L, int H);  // workspace layout, below
+
+template <int DT, int D>
+int bwd_16(int B, int L, int H, float scale, const void *q, const void *k, const void *v, long long ld,
+           const void *o, const float *lse, const void *dout, void *dq, void *dk, void *dv, long long ldd,
+           float *nrow, hipStream_t st) {  // nrow: the workspace (row constants, then Q * c)
+    using T = typename Ty<DT>::T;
+    T *qc = reinterpret_cast<T *>(reinterpret_cast<char *>(nrow) + qc_offset(B, L, H));
+    constexpr int S2 = D <= 32 ? 2 : 1;  // two 16-row sub-tiles per wavefront where registers allow
+    const bool two = S2 == 2 && (long long)((L + 127) / 128) * B * H >= 512;
+    dim3 g2((L + (two ? 127 : 63)) / (two ? 128 : 64), B * H);
+    if (two) {
+        LGM_LAUNCH("k_attn_dq", st, (k_attn_dq2<DT, D, S2><<<g2, NT, 0, st>>>(L, H, scale, (const T *)q,
+                   (const T *)k, (const T *)v, ld, (const T *)dout, lse, nrow, (T *)dq, ldd, (const T *)o, qc)));
+        LGM_LAUNCH("k_attn_dkdv", st, (k_attn_dkdv2<DT, D, S2><<<g2, NT, 0, st>>>(L, H, scale, (const T *)qc,
+                   (const T *)k, (const T *)v, ld, (const T *)dout, nrow, (T *)dk, (T *)dv, ldd)));
+    } else {
+        LGM_LAUNCH("k_attn_dq", st, (k_attn_dq2<DT, D, 1><<<g2, NT, 0, st>>>(L, H, scale, (const T *)q,
+                   (const T *)k, (const T *)v, ld, (const T *)dout, lse, nrow, (T *)dq, ldd, (const T *)o, qc)));
+        LGM_LAUNCH("k_attn_dkdv", st, (k_attn_dkdv2<DT, D, 1><<<g2, NT, 0, st>>>(L, H, scale, (const T *)qc,
+                   (const T *)k, (const T *)v, ld, (const T *)dout, nrow, (T *)dk, (T *)dv, ldd)));
+    }
+    return LGM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // backward workspace. fp32: delta [B*H][L]. 16-bit: -lse' and -delta [2][B*H][row_pitch(L)] fp32, then
 // Q * scale * log2(e) [B*H][L][D] in the input type.
 size_t qc_offset(int B, int L, int H) {
     return (2 * (size_t)B * H * row_pitch(L) * sizeof(float) + 255) & ~(size_t)255;
-}
-
-template <int DT, int D>
-int bwd_impl(int B, int L, int H, float scale, const void *q, const void *k, const void *v, long long ld,
-             const void *o, const float *lse, const void *dout, void *dq, void *dk, void *dv, long long ldd,
-             float *delta, hipStream_t st) {
-    using T = typename Ty<DT>::T;
-    const long long rows = (long long)B * L * H;
-    T *qc = reinterpret_cast<T *>(reinterpret_cast<char *>(delta) + qc_offset(B, L, H));  // (16-bit paths)
-    if constexpr (DT != LGM_ATTN_F32) {  // (delta computed by k_attn_dq2 itself)
-        constexpr int S2 = D <= 32 ? 2 : 1;  // two 16-row sub-tiles per wavefront where registers allow
-        const bool two = S2 == 2 && (long long)((L + 127) / 128) * B * H >= 512;
-        dim3 g2((L + (two ? 127 : 63)) / (two ? 128 : 64), B * H);
-        if (two) {
-            LGM_LAUNCH("k_attn_dq", st, (k_attn_dq2<DT, D, S2><<<g2, NT, 0, st>>>(L, H, scale, (const T *)q,
-                       (const T *)k, (const T *)v, ld, (const T *)dout, lse, delta, (T *)dq, ldd, (const T *)o, qc)));
-            LGM_LAUNCH("k_attn_dkdv", st, (k_attn_dkdv2<DT, D, S2><<<g2, NT, 0, st>>>(L, H, scale, (const T *)qc,
-                       (const T *)k, (const T *)v, ld, (const T *)dout, delta, (T *)dk, (T *)dv, ldd)));
-        } else {
-            LGM_LAUNCH("k_attn_dq", st, (k_attn_dq2<DT, D, 1><<<g2, NT, 0, st>>>(L, H, scale, (const T *)q,
-                       (const T *)k, (const T *)v, ld, (const T *)dout, lse, delta, (T *)dq, ldd, (const T *)o, qc)));
-            LGM_LAUNCH("k_attn_dkdv", st, (k_attn_dkdv2<DT, D, 1><<<g2, NT, 0, st>>>(L, H, scale, (const T *)qc,
-                       (const T *)k, (const T *)v, ld, (const T *)dout, delta, (T *)dk, (T *)dv, ldd)));
-        }
-        return LGM_OK;
-    }
-    LGM_LAUNCH("k_attn_delta", st, (k_attn_delta<DT, D><<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(
-                                       B, L, H, (const T *)o, (const T *)dout, delta)));
-    dim3 grid((L + 63) / 64, B * H);
-    LGM_LAUNCH("k_attn_dq", st, (k_attn_dq<DT, D><<<grid, NT, 0, st>>>(L, H, scale, (const T *)q, (const T *)k,
-                                                                     (const T *)v, ld, (const T *)dout, lse, delta,
-                                                                     (T *)dq, ldd)));
-    LGM_LAUNCH("k_attn_dkdv", st, (k_attn_dkdv<DT, D><<<grid, NT, 0, st>>>(L, H, scale, (const T *)q, (const T *)k,
-                                                                         (const T *)v, ld, (const T *)dout, lse,
-                                                                         delta, (T *)dk, (T *)dv, ldd)));
-    return LGM_OK;
 }
 
 int check(int dtype, int B, int L, int H, int D) {
@@ -1196,18 +1155,20 @@ int check(int dtype, int B, int L, int H, int D) {
 }  // namespace attn
 }  // namespace lgm
 
-#define LGM_ATTN_DISPATCH(FN, ...)                                                                             \
-    switch (dtype * 1000 + D) {                                                                                \
-        case LGM_ATTN_F32 * 1000 + 32: return lgm::attn::FN<LGM_ATTN_F32, 32>(__VA_ARGS__);                   \
-        case LGM_ATTN_F32 * 1000 + 64: return lgm::attn::FN<LGM_ATTN_F32, 64>(__VA_ARGS__);                   \
-        case LGM_ATTN_F32 * 1000 + 128: return lgm::attn::FN<LGM_ATTN_F32, 128>(__VA_ARGS__);                 \
-        case LGM_ATTN_BF16 * 1000 + 32: return lgm::attn::FN<LGM_ATTN_BF16, 32>(__VA_ARGS__);                 \
-        case LGM_ATTN_BF16 * 1000 + 64: return lgm::attn::FN<LGM_ATTN_BF16, 64>(__VA_ARGS__);                 \
-        case LGM_ATTN_BF16 * 1000 + 128: return lgm::attn::FN<LGM_ATTN_BF16, 128>(__VA_ARGS__);               \
-        case LGM_ATTN_F16 * 1000 + 32: return lgm::attn::FN<LGM_ATTN_F16, 32>(__VA_ARGS__);                   \
-        case LGM_ATTN_F16 * 1000 + 64: return lgm::attn::FN<LGM_ATTN_F16, 64>(__VA_ARGS__);                   \
-        case LGM_ATTN_F16 * 1000 + 128: return lgm::attn::FN<LGM_ATTN_F16, 128>(__VA_ARGS__);                 \
-        default: return LGM_E_INVALID;                                                                         \
+// The element type picks the path (FN_f32 | FN_16), then D the instantiation (HD in the call).
+#define LGM_ATTN_BY_D(...)                                                   \
+    switch (D) {                                                             \
+        case 32: { constexpr int HD = 32; return lgm::attn::__VA_ARGS__; }   \
+        case 64: { constexpr int HD = 64; return lgm::attn::__VA_ARGS__; }   \
+        case 128: { constexpr int HD = 128; return lgm::attn::__VA_ARGS__; } \
+        default: return LGM_E_INVALID;                                       \
+    }
+#define LGM_ATTN_DISPATCH(FN, ...)                                                     \
+    switch (dtype) {                                                                   \
+        case LGM_ATTN_F32: LGM_ATTN_BY_D(FN##_f32<HD>(__VA_ARGS__))                    \
+        case LGM_ATTN_BF16: LGM_ATTN_BY_D(FN##_16<LGM_ATTN_BF16, HD>(__VA_ARGS__))     \
+        case LGM_ATTN_F16: LGM_ATTN_BY_D(FN##_16<LGM_ATTN_F16, HD>(__VA_ARGS__))       \
+        default: return LGM_E_INVALID;                                                 \
     }
 
 extern "C" {
@@ -1229,7 +1190,7 @@ int lgm_attn_forward(int dtype, int B, int L, int H, int D, float scale, const v
         return LGM_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    LGM_ATTN_DISPATCH(fwd_impl, B, L, H, scale, q, k, v, ld_qkv, o, lse, st)
+    LGM_ATTN_DISPATCH(fwd, B, L, H, scale, q, k, v, ld_qkv, o, lse, st)
 }
 
 int lgm_attn_backward(int dtype, int B, int L, int H, int D, float scale, const void *q, const void *k,
@@ -1249,7 +1210,7 @@ int lgm_attn_backward(int dtype, int B, int L, int H, int D, float scale, const 
         return LGM_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    LGM_ATTN_DISPATCH(bwd_impl, B, L, H, scale, q, k, v, ld_qkv, o, lse, d_o, dq, dk, dv, ld_dqkv,
+    LGM_ATTN_DISPATCH(bwd, B, L, H, scale, q, k, v, ld_qkv, o, lse, d_o, dq, dk, dv, ld_dqkv,
                       (float *)workspace, st)
 }
 

@@ -368,6 +368,29 @@ def test_attention_deterministic(cuda):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_attention_kernels_per_dtype(cuda, dtype):
+    """The kernels each element type runs (attention.hip's header): fp32 has a separate delta pass before dQ and
+    dK/dV; the 16-bit backward has none (k_attn_dq2 computes delta itself). One forward and backward of one full
+    64-row tile plus a one-row tail: every kernel is launched exactly once."""
+    from lgm_amd import _native
+    from lgm_amd.attention import packed_attention
+    B, L, H, D = 1, 65, 2, 32
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(B, L, 3, H, D, generator=gen).to(cuda, dtype).requires_grad_(True)
+    d_o = torch.randn(B, L, H, D, generator=gen).to(cuda, dtype)
+    prof = _native.KernelProfiler()
+    with prof:
+        packed_attention(x).backward(d_o)
+    torch.cuda.synchronize()
+    ran = prof.summary()
+    prof.close()
+    want = {"k_attn_fwd", "k_attn_dq", "k_attn_dkdv"} | ({"k_attn_delta"} if dtype == torch.float32 else set())
+    assert set(ran) == want, sorted(ran)
+    assert all(n == 1 for n, _ in ran.values()), ran
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("where", ["q", "k", "v"])
 def test_nan_propagates_like_sdpa(cuda, dtype, where):
