@@ -68,6 +68,9 @@ SIGNATURES = {
     "lgm_linear_wgrad_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
     "lgm_linear_wgrad": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp, _c_size,
                                   _vp, _vp]),
+    "lgm_conv_wgrad_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "lgm_conv_wgrad": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_size,
+                                _vp, _vp]),
     "lgm_gn_silu_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "lgm_gn_silu_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _c_size, _vp, _vp]),

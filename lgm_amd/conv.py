@@ -1,0 +1,126 @@
+"""The UNet's stride-1 3 x 3 and 1 x 1 convolutions (core/unet.py: ResnetBlock conv1 / conv2 / shortcut, UpBlock
+upsample, UNet conv_in / conv_out) under 16-bit autocast, with the weight and bias gradients on the HIP split-K MFMA
+kernel (lgm_amd/csrc/conv_wgrad.hip, include/lgm_conv.h).
+
+The forward and the input gradient are the library convolutions torch's autocast runs for nn.Conv2d (F.conv2d on the
+16-bit casts of input, weight and bias; aten.convolution_backward for the input alone). The weight and bias gradients
+-- reductions over every pixel of the batch -- come from lgm_conv_wgrad, in fp32 straight into the fp32 parameters'
+gradients (torch rounds them to the autocast dtype first and casts back). fp32 convolutions (no autocast), strided,
+dilated, grouped and other kernel sizes stay on torch.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _native as nat
+
+_CODES = {torch.bfloat16: 1, torch.float16: 2}  # include/lgm_attn.h LGM_ATTN_BF16 / LGM_ATTN_F16
+_GRID_MAX = 2 ** 31 - 1
+
+
+def wgrad(dy: torch.Tensor, x: torch.Tensor, ksize: int, want_db: bool):
+    """lgm_conv_wgrad on dense NCHW 16-bit GPU tensors dy [N, Cout, H, W] and x [N, Cin, H, W]: (dw fp32
+    [Cout, Cin, ksize, ksize], db fp32 [Cout] or None). The tensors may start at any element of their storage."""
+    N, Cout, H, W = dy.shape
+    Cin = x.shape[1]
+    dw = torch.empty((Cout, Cin, ksize, ksize), device=dy.device, dtype=torch.float32)
+    db = torch.empty((Cout,), device=dy.device, dtype=torch.float32) if want_db else None
+    L = nat.lib()
+    ws_bytes = L.lgm_conv_wgrad_workspace_size(N, Cin, Cout, H, W, ksize, int(want_db))
+    ws = torch.empty(max(ws_bytes, 1), device=dy.device, dtype=torch.uint8)
+    nat.check(L.lgm_conv_wgrad(_CODES[dy.dtype], N, Cin, Cout, H, W, ksize, nat.ptr(dy), nat.ptr(x), nat.ptr(dw),
+                               nat.ptr(db), nat.ptr(ws), ws_bytes, nat.stream_of(dy.device), nat.diag()),
+              "lgm_conv_wgrad")
+    return dw, db
+
+
+class _Conv16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, dt, pad: int):
+        with torch.autocast("cuda", enabled=False):
+            x16 = x.to(dt)
+            w16 = weight.to(dt)
+            out = F.conv2d(x16, w16, None if bias is None else bias.to(dt), 1, pad)
+        ctx.save_for_backward(x16, w16)
+        ctx.meta = (x.dtype, weight.dtype, None if bias is None else bias.dtype, dt, pad)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x16, w16 = ctx.saved_tensors
+        xdt, wdt, bdt, dt, pad = ctx.meta
+        g16 = g.to(dt)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            with torch.autocast("cuda", enabled=False):
+                gx = torch.ops.aten.convolution_backward(g16, x16, w16, None, [1, 1], [pad, pad], [1, 1], False, [0, 0],
+                                                         1, [True, False, False])[0].to(xdt)
+        dw = db = None
+        want_w = ctx.needs_input_grad[1]
+        want_b = bdt is not None and ctx.needs_input_grad[2]
+        if want_w or want_b:
+            # dense NCHW for the C ABI (a channels_last activation or gradient is copied; a view into a larger buffer
+            # that is already dense goes as it is, at whatever element it starts: the kernel takes any alignment)
+            dw, db = wgrad(g16.contiguous(), x16.contiguous(), w16.shape[-1], want_b)
+            dw = dw.to(wdt) if want_w else None
+            db = None if db is None else db.to(bdt)
+        return gx, dw, db, None, None
+
+
+# (Cin, Cout, H, W, ksize) on which MIOpen's weight + bias gradient measured faster than k_conv_wgrad at 4 or at 32 views
+# (DESIGN §4 "Conv weight gradient", profiles/conv_wgrad/bench_conv.json): one of the 43 stride-1 shapes of LGM 'big'
+_TORCH_FASTER = {(768, 256, 64, 64, 3)}
+
+
+def _shape_goes_native(Cin: int, Cout: int, H: int, W: int, ksize: int) -> bool:
+    """The dispatch rule: a shape goes to the kernel unless the table has it slower than torch's arm at either view
+    count by more than the spread between two runs (shapes the table does not have go to the kernel: it won or tied
+    on 85 of its 86 rows)."""
+    return (Cin, Cout, H, W, ksize) not in _TORCH_FASTER
+
+
+def _takes(x: torch.Tensor, conv: nn.Conv2d):
+    """(autocast dtype, padding) where lgm_conv_wgrad serves this call, else None."""
+    if not isinstance(conv, nn.Conv2d) or not isinstance(x, torch.Tensor) or x.dim() != 4 or not x.is_cuda:
+        return None
+    w = conv.weight
+    if w.device != x.device or (conv.bias is not None and conv.bias.device != x.device):
+        return None
+    if torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        if not x.is_floating_point():
+            return None
+    elif x.dtype in _CODES and w.dtype == x.dtype:
+        dt = x.dtype
+    else:
+        return None
+    k = conv.kernel_size[0]
+    if dt not in _CODES or conv.kernel_size not in ((1, 1), (3, 3)) or conv.stride != (1, 1) or \
+            conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros" or conv.transposed:
+        return None
+    pad = (k - 1) // 2
+    if conv.padding != (pad, pad) and conv.padding != "same":
+        return None
+    N, C, H, W = x.shape
+    if C != conv.in_channels or x.numel() == 0 or N * H > _GRID_MAX:
+        return None
+    tiles = (-(-conv.out_channels // 64)) * (-(-C // 64))
+    if tiles * 9 * 16 > _GRID_MAX or not _shape_goes_native(C, conv.out_channels, H, W, k):
+        return None
+    return dt, pad
+
+
+def conv2d(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
+    """conv(x), with the HIP weight / bias gradient where the convolution runs in 16 bits on the GPU (under bf16 / fp16
+    autocast, or a 16-bit module on a 16-bit input), is stride 1, dilation 1, groups 1, 1 x 1 or 3 x 3 with zero padding
+    of (k - 1) / 2, and the shape is one the kernel is not slower on. Anything else -- fp32, CPU tensors, stride 2, other
+    kernels and paddings -- is conv(x), and so is a call that records no graph (inference)."""
+    if not (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or
+                                         (conv.bias is not None and conv.bias.requires_grad))):
+        return conv(x)
+    t = _takes(x, conv)
+    if t is None:
+        return conv(x)
+    return _Conv16.apply(x, conv.weight, conv.bias, t[0], t[1])

@@ -6,8 +6,10 @@ forward signatures of the reference, and create their parameters in the same ord
 with strict=True and a seeded construction draws the same weights. Every GroupNorm -> SiLU (-> resample) site goes
 through `group_norm_silu`, one HIP pass per direction, while `fused` (a plain attribute, default True) is set;
 fused = False runs torch ops as upstream. Attention head dims outside the flash kernels' 32 / 64 / 128 (no LGM preset
-has one; test-sized UNets do) take the reference's own fallback attention in torch ops. The convolutions, torch.cat
-and the residual (x + shortcut(res)) * skip_scale stay torch. Additive: UNet(..., num_frames=4) is passed to every MVAttention (the reference hard-codes 4).
+has one; test-sized UNets do) take the reference's own fallback attention in torch ops. The stride-1 convolutions go
+through lgm_amd.conv.conv2d while `native_wgrad` (a plain attribute, default True) is set: torch's forward and input
+gradient, the weight / bias gradient on the HIP split-K kernel (include/lgm_conv.h); the stride-2 downsample
+convolutions, torch.cat and the residual (x + shortcut(res)) * skip_scale stay torch. Additive: UNet(..., num_frames=4) is passed to every MVAttention (the reference hard-codes 4).
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from .attention import _DTYPES, MemEffAttention, MVAttention, _autocast_dtype
+from .conv import conv2d
 from .cpu import attention_cpu
 
 _RESAMPLE = {None: 0, "default": 0, "up": 1, "down": 2}  # include/lgm_norm.h LGM_GN_RESAMPLE_*
@@ -171,6 +174,7 @@ class ResnetBlock(nn.Module):
         if self.in_channels != self.out_channels:
             self.shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, bias=True)
         self.fused = True  # the HIP GroupNorm+SiLU(+resample) kernels (False: torch ops, as upstream)
+        self.native_wgrad = True  # the HIP conv weight gradient while fused (False: torch's autograd through the convs)
 
     def _resample(self, t):
         if self.resample_mode == "up":
@@ -179,11 +183,12 @@ class ResnetBlock(nn.Module):
 
     def forward(self, x):
         res = x
+        native = self.fused and self.native_wgrad
         if self.fused:
             x = group_norm_silu(x, self.norm1, self.resample_mode)
             if self.resample_mode:
                 res = self._resample(res)
-            x = self.conv1(x)
+            x = conv2d(x, self.conv1) if native else self.conv1(x)
             x = group_norm_silu(x, self.norm2)
         else:
             x = self.act(self.norm1(x))
@@ -192,8 +197,9 @@ class ResnetBlock(nn.Module):
                 x = self._resample(x)
             x = self.conv1(x)
             x = self.act(self.norm2(x))
-        x = self.conv2(x)
-        return (x + self.shortcut(res)) * self.skip_scale
+        x = conv2d(x, self.conv2) if native else self.conv2(x)
+        res = conv2d(res, self.shortcut) if native and self.in_channels != self.out_channels else self.shortcut(res)
+        return (x + res) * self.skip_scale
 
 
 class DownBlock(nn.Module):
@@ -270,6 +276,7 @@ class UpBlock(nn.Module):
         self.upsample = None
         if upsample:
             self.upsample = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
+        self.native_wgrad = True  # the HIP conv weight gradient of `upsample`, while the block's ResnetBlocks are fused
 
     def forward(self, x, xs):
         for attn, net in zip(self.attns, self.nets):
@@ -281,7 +288,8 @@ class UpBlock(nn.Module):
                 x = attn(x)
         if self.upsample:
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-            x = self.upsample(x)
+            native = self.native_wgrad and self.nets[0].fused
+            x = conv2d(x, self.upsample) if native else self.upsample(x)
         return x
 
 
@@ -317,6 +325,20 @@ class UNet(nn.Module):
         self.norm_out = nn.GroupNorm(num_channels=up_channels[-1], num_groups=32, eps=1e-5)
         self.conv_out = nn.Conv2d(up_channels[-1], out_channels, kernel_size=3, stride=1, padding=1)
         self._fused = True
+        self._native_wgrad = True
+
+    @property
+    def native_wgrad(self) -> bool:
+        """The HIP conv weight gradient at conv_in / conv_out (while `fused`); setting it sets every ResnetBlock's and
+        UpBlock's `native_wgrad` too (the MVAttention blocks keep their own switch for their Linears)."""
+        return self._native_wgrad
+
+    @native_wgrad.setter
+    def native_wgrad(self, value: bool):
+        self._native_wgrad = bool(value)
+        for m in self.modules():
+            if isinstance(m, (ResnetBlock, UpBlock)):
+                m.native_wgrad = bool(value)
 
     @property
     def fused(self) -> bool:
@@ -332,7 +354,8 @@ class UNet(nn.Module):
                 m.fused = bool(value)
 
     def forward(self, x):
-        x = self.conv_in(x)
+        native = self._fused and self._native_wgrad
+        x = conv2d(x, self.conv_in) if native else self.conv_in(x)
         xss = [x]
         for block in self.down_blocks:
             x, xs = block(x)
@@ -343,4 +366,4 @@ class UNet(nn.Module):
             xss = xss[:-len(block.nets)]
             x = block(x, xs)
         x = group_norm_silu(x, self.norm_out) if self._fused else F.silu(self.norm_out(x))
-        return self.conv_out(x)
+        return conv2d(x, self.conv_out) if native else self.conv_out(x)
