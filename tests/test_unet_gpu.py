@@ -12,8 +12,8 @@ import torch.nn.functional as F
 
 from lgm_amd import LGM, Options, UNet
 from lgm_amd import _native as nat
-from lgm_amd.cameras import default_rays, orbit_cameras
 from tests.golden.make_unet_golden import GRAD_PARAMS, TINY
+from tests.lgm_ref import lgm_data
 from tests.render_cases import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -139,19 +139,6 @@ def test_num_frames_2(cuda):
     ga, gb = grouped(gpa), grouped(gpb)
     for k in ga:
         assert relv(ga[k], gb[k]) < 1e-5, k
-
-
-def lgm_data(cuda, B=2, Vo=2, S=32, size=16, seed=0):
-    gen = torch.Generator().manual_seed(seed)
-    rays = default_rays(size)  # [4, 6, size, size]
-    images = torch.randn(B, 4, 3, size, size, generator=gen)
-    inp = torch.cat([images, rays[None].expand(B, -1, -1, -1, -1)], dim=2)
-    cv, cvp, cp = orbit_cameras(Vo, azimuth_offset=20.0)
-    masks = (torch.rand(B, Vo, 1, S, S, generator=gen) > 0.5).float()
-    data = {"input": inp, "cam_view": cv[None].expand(B, -1, -1, -1), "cam_view_proj": cvp[None].expand(B, -1, -1, -1),
-            "cam_pos": cp[None].expand(B, -1, -1), "images_output": torch.rand(B, Vo, 3, S, S, generator=gen),
-            "masks_output": masks}
-    return {k: v.contiguous().to(cuda) for k, v in data.items()}
 
 
 def test_lgm_forward_backward(cuda):
