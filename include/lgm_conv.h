@@ -1,10 +1,11 @@
 /*
- * lgm_conv.h -- C ABI of the weight / bias gradient of the UNet's convolutions in liblgm_amd.so
- * (lgm_amd/csrc/conv_wgrad.hip).
+ * lgm_conv.h -- C ABI of the UNet's convolutions in liblgm_amd.so: the weight / bias gradient
+ * (lgm_amd/csrc/conv_wgrad.hip), and the forward and the input gradient (lgm_amd/csrc/conv_fwd.hip, below).
  *
- * Replaces the weight / bias part of autograd through nn.Conv2d for the stride-1 3 x 3 and 1 x 1 convolutions of
- * core/unet.py (ResnetBlock conv1 / conv2 / shortcut, UpBlock upsample, UNet conv_in / conv_out) under accelerate's bf16
- * (or fp16) autocast. The forward and the input gradient stay on the library convolution.
+ * lgm_conv_wgrad replaces the weight / bias part of autograd through nn.Conv2d for the stride-1 3 x 3 and 1 x 1
+ * convolutions of core/unet.py (ResnetBlock conv1 / conv2 / shortcut, UpBlock upsample, UNet conv_in / conv_out) under
+ * accelerate's bf16 (or fp16) autocast. The forward and the input gradient are the library convolution unless the caller
+ * opts into lgm_conv_forward / lgm_conv_dgrad.
  *
  * Operation. Stride 1, dilation 1, groups 1, padding p = (ksize - 1) / 2, ksize in {1, 3}:
  *
@@ -49,6 +50,52 @@ extern "C" {
 size_t lgm_conv_wgrad_workspace_size(int N, int Cin, int Cout, int H, int W, int ksize, int want_db);
 int lgm_conv_wgrad(int dtype, int N, int Cin, int Cout, int H, int W, int ksize, const void *dy, const void *x,
                    float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream, const lgm_diag *diag);
+
+/*
+ * lgm_conv_forward / lgm_conv_dgrad -- the forward and the input gradient of the same convolutions.
+ *
+ * Operation. Stride 1, dilation 1, groups 1, padding p = (ksize - 1) / 2, ksize in {1, 3}:
+ *
+ *   y[n][co][y][x]  = bias[co] + sum over ci, ky, kx of w[co][ci][ky][kx] * X[n][ci][y + ky - p][x + kx - p]
+ *   dx[n][ci][y][x] =            sum over co, ky, kx of w[co][ci][ky][kx] * DY[n][co][y - ky + p][x - kx + p]
+ *
+ * with X = x (DY = dy) inside the image and zero outside it: never a neighbouring row's, channel's or sample's
+ * elements. The input gradient is the forward on the transposed, tap-flipped weight; both run one kernel body, the
+ * weight index map is a mode of the packing pass.
+ *
+ * Operands. x is [N][Cin][H][W], y and dy are [N][Cout][H][W], dx is [N][Cin][H][W]: dense NCHW of `dtype`
+ * LGM_ATTN_BF16 or LGM_ATTN_F16. w is [Cout][Cin][ksize][ksize] contiguous, of w_dtype = dtype or LGM_ATTN_F32; fp32
+ * weights are rounded to dtype, round to nearest even (as tensor.to(dt)), by k_conv_wpack, which runs once per call and
+ * writes the K-contiguous tiles the MFMA operand needs into the workspace. bias is NULL or [Cout] of bias_dtype = dtype
+ * or LGM_ATTN_F32 (rounded to dtype like the weight, as autocast's cast of it does; bias_dtype is ignored where bias is
+ * NULL). Any Cin, Cout, H, W >= 1. Pointers need only element
+ * alignment (fp32 ones 4 bytes): activations are read element by element, and an output's four pixels go as one
+ * 8-byte store where they are in one row and 8-byte aligned and as four 2-byte stores otherwise -- the same bits.
+ *
+ * Numerics. Products are exact and accumulated in fp32 on v_mfma_f32_16x16x32_{bf16,f16}, the bias is added in fp32,
+ * then one rounding to the 16-bit output. The K range (the input channels, in steps of 32 with all their taps) may be
+ * split S ways (small images with many channels): the S fp32 partials live in the workspace and are summed in split
+ * order, then bias, then the rounding. Every sum runs in an order that is a function of (N, Cin, Cout, H, W, ksize)
+ * only. No floating atomics: two calls give equal bits.
+ *
+ * Degenerate sizes. N * H * W == 0, or no output channel (Cout == 0 forward, Cin == 0 input gradient): rc 0, nothing
+ * written. Cin == 0 forward writes the bias (zeros if NULL); Cout == 0 input gradient writes zeros.
+ *
+ * Errors. rc < 0 with lgm_last_error() set and nothing launched on: a dtype outside the two, a w_dtype / bias_dtype that
+ * is neither fp32 nor dtype; ksize outside {1, 3}; a negative size; a null x / dy / w / y / dx with work to do; a grid
+ * beyond 2^31 - 1 workgroups; a workspace shorter than lgm_conv_{forward,dgrad}_workspace_size (any contents; it holds
+ * the packed weight and the split partials).
+ *
+ * All element offsets are 64-bit. Everything is enqueued on `stream`; nothing synchronises. Profiler labels:
+ * k_conv_wpack, then k_conv_fwd or k_conv_dgrad, then k_conv_fwd_reduce where the K range is split.
+ */
+size_t lgm_conv_forward_workspace_size(int N, int Cin, int Cout, int H, int W, int ksize);
+int lgm_conv_forward(int dtype, int w_dtype, int N, int Cin, int Cout, int H, int W, int ksize, const void *x,
+                     const void *w, const void *bias, int bias_dtype, void *y, void *workspace, size_t workspace_bytes,
+                     void *stream, const lgm_diag *diag);
+size_t lgm_conv_dgrad_workspace_size(int N, int Cin, int Cout, int H, int W, int ksize);
+int lgm_conv_dgrad(int dtype, int w_dtype, int N, int Cin, int Cout, int H, int W, int ksize, const void *dy,
+                   const void *w, void *dx, void *workspace, size_t workspace_bytes, void *stream, const lgm_diag *diag);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,12 @@ SIGNATURES = {
     "lgm_conv_wgrad_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "lgm_conv_wgrad": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_size,
                                 _vp, _vp]),
+    "lgm_conv_forward_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "lgm_conv_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int,
+                                  _vp, _vp, _c_size, _vp, _vp]),
+    "lgm_conv_dgrad_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "lgm_conv_dgrad": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,
+                                _c_size, _vp, _vp]),
     "lgm_gn_silu_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "lgm_gn_silu_forward": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _c_size, _vp, _vp]),
@@ -102,7 +108,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN

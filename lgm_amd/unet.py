@@ -9,7 +9,9 @@ fused = False runs torch ops as upstream. Attention head dims outside the flash 
 has one; test-sized UNets do) take the reference's own fallback attention in torch ops. The stride-1 convolutions go
 through lgm_amd.conv.conv2d while `native_wgrad` (a plain attribute, default True) is set: torch's forward and input
 gradient, the weight / bias gradient on the HIP split-K kernel (include/lgm_conv.h); the stride-2 downsample
-convolutions, torch.cat and the residual (x + shortcut(res)) * skip_scale stay torch. Additive: UNet(..., num_frames=4) is passed to every MVAttention (the reference hard-codes 4).
+convolutions, torch.cat and the residual (x + shortcut(res)) * skip_scale stay torch. `native_conv` (a plain attribute,
+default False) sends the same convolutions through lgm_amd.conv.conv2d_native instead: forward and input gradient on the
+HIP implicit-GEMM kernel as well, with or without a recorded graph. Additive: UNet(..., num_frames=4) is passed to every MVAttention (the reference hard-codes 4).
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from .attention import _DTYPES, MemEffAttention, MVAttention, _autocast_dtype
-from .conv import conv2d
+from .conv import conv2d, conv2d_native
 from .cpu import attention_cpu
 
 _RESAMPLE = {None: 0, "default": 0, "up": 1, "down": 2}  # include/lgm_norm.h LGM_GN_RESAMPLE_*
@@ -155,6 +157,14 @@ def group_norm_silu(x: torch.Tensor, norm: nn.GroupNorm, resample=None) -> torch
     return _GnSilu.apply(x, norm.weight, norm.bias, norm.num_groups, norm.eps, rs, y_dtype)
 
 
+def _conv_site(x, conv: nn.Conv2d, wgrad: bool, native_conv: bool):
+    """One stride-1 convolution of a fused block: every direction on the HIP kernels (native_conv), the weight gradient
+    alone (wgrad: the module-level conv2d), or the module itself."""
+    if native_conv:
+        return conv2d_native(x, conv)
+    return conv2d(x, conv) if wgrad else conv(x)
+
+
 class ResnetBlock(nn.Module):
     """core/unet.py:51-103."""
 
@@ -175,6 +185,7 @@ class ResnetBlock(nn.Module):
             self.shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, bias=True)
         self.fused = True  # the HIP GroupNorm+SiLU(+resample) kernels (False: torch ops, as upstream)
         self.native_wgrad = True  # the HIP conv weight gradient while fused (False: torch's autograd through the convs)
+        self.native_conv = False  # the HIP conv forward and input gradient too, while fused (opt-in)
 
     def _resample(self, t):
         if self.resample_mode == "up":
@@ -184,11 +195,12 @@ class ResnetBlock(nn.Module):
     def forward(self, x):
         res = x
         native = self.fused and self.native_wgrad
+        nconv = self.fused and self.native_conv
         if self.fused:
             x = group_norm_silu(x, self.norm1, self.resample_mode)
             if self.resample_mode:
                 res = self._resample(res)
-            x = conv2d(x, self.conv1) if native else self.conv1(x)
+            x = _conv_site(x, self.conv1, native, nconv)
             x = group_norm_silu(x, self.norm2)
         else:
             x = self.act(self.norm1(x))
@@ -197,8 +209,11 @@ class ResnetBlock(nn.Module):
                 x = self._resample(x)
             x = self.conv1(x)
             x = self.act(self.norm2(x))
-        x = conv2d(x, self.conv2) if native else self.conv2(x)
-        res = conv2d(res, self.shortcut) if native and self.in_channels != self.out_channels else self.shortcut(res)
+        x = _conv_site(x, self.conv2, native, nconv)
+        if self.in_channels != self.out_channels:
+            res = _conv_site(res, self.shortcut, native, nconv)
+        else:
+            res = self.shortcut(res)
         return (x + res) * self.skip_scale
 
 
@@ -277,6 +292,7 @@ class UpBlock(nn.Module):
         if upsample:
             self.upsample = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
         self.native_wgrad = True  # the HIP conv weight gradient of `upsample`, while the block's ResnetBlocks are fused
+        self.native_conv = False  # its forward and input gradient on the HIP kernel too (opt-in)
 
     def forward(self, x, xs):
         for attn, net in zip(self.attns, self.nets):
@@ -288,8 +304,8 @@ class UpBlock(nn.Module):
                 x = attn(x)
         if self.upsample:
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-            native = self.native_wgrad and self.nets[0].fused
-            x = conv2d(x, self.upsample) if native else self.upsample(x)
+            fused = self.nets[0].fused
+            x = _conv_site(x, self.upsample, self.native_wgrad and fused, self.native_conv and fused)
         return x
 
 
@@ -326,6 +342,20 @@ class UNet(nn.Module):
         self.conv_out = nn.Conv2d(up_channels[-1], out_channels, kernel_size=3, stride=1, padding=1)
         self._fused = True
         self._native_wgrad = True
+        self._native_conv = False
+
+    @property
+    def native_conv(self) -> bool:
+        """The HIP conv forward and input gradient at conv_in / conv_out (while `fused`); setting it sets every
+        ResnetBlock's and UpBlock's `native_conv` too. Off by default."""
+        return self._native_conv
+
+    @native_conv.setter
+    def native_conv(self, value: bool):
+        self._native_conv = bool(value)
+        for m in self.modules():
+            if isinstance(m, (ResnetBlock, UpBlock)):
+                m.native_conv = bool(value)
 
     @property
     def native_wgrad(self) -> bool:
@@ -355,7 +385,8 @@ class UNet(nn.Module):
 
     def forward(self, x):
         native = self._fused and self._native_wgrad
-        x = conv2d(x, self.conv_in) if native else self.conv_in(x)
+        nconv = self._fused and self._native_conv
+        x = _conv_site(x, self.conv_in, native, nconv)
         xss = [x]
         for block in self.down_blocks:
             x, xs = block(x)
@@ -366,4 +397,4 @@ class UNet(nn.Module):
             xss = xss[:-len(block.nets)]
             x = block(x, xs)
         x = group_norm_silu(x, self.norm_out) if self._fused else F.silu(self.norm_out(x))
-        return conv2d(x, self.conv_out) if native else self.conv_out(x)
+        return _conv_site(x, self.conv_out, native, nconv)

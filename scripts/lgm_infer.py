@@ -5,7 +5,10 @@ and N orbit frames through lgm_amd.cameras.render_orbit_frames. Runs on the GPU 
 (torch paths of lgm_amd/cpu.py). Without --ckpt the weights are a seeded random init (no checkpoint exists offline).
 
     python scripts/lgm_infer.py [--png tests/golden/catstatue_rgba.png] [--ckpt STATE_DICT.pt] [--frames 8]
-                                [--device cuda|cpu] [--bf16] [--out bench_out_lgm_infer]
+                                [--device cuda|cpu] [--bf16] [--native-conv] [--out bench_out_lgm_infer]
+
+--native-conv (with --bf16 on the GPU) runs the UNet's stride-1 convolutions on the HIP kernel (UNet.native_conv)
+instead of the library convolution: no first-call solver search.
 """
 from __future__ import annotations
 
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--frames", type=int, default=8, help="orbit frames to render")
     ap.add_argument("--render-size", type=int, default=256)
     ap.add_argument("--bf16", action="store_true", help="run the model under bf16 autocast (GPU)")
+    ap.add_argument("--native-conv", action="store_true",
+                    help="the UNet's stride-1 convolutions on the HIP kernel (16-bit on the GPU: with --bf16)")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -55,6 +60,7 @@ def main():
         sd = torch.load(a.ckpt, map_location="cpu", weights_only=True)
         model.load_state_dict(sd.get("model", sd) if isinstance(sd, dict) else sd, strict=True)
     model = model.to(dev).eval()
+    model.unet.native_conv = bool(a.native_conv)
     t["build_s"] = time.perf_counter() - t0
     images = load_views(a.png, opt.input_size).to(dev)  # [1, 4, 9, 256, 256]
     with torch.no_grad():
