@@ -99,6 +99,15 @@ SIGNATURES = {
     "lgm_optim_adamw": (_c_int, [_vp, _c_int, _vp, _c_ll, _c_ll, _vp, _c_double, _c_double, _c_double, _c_double,
                                  _c_double, _c_double, _vp, _vp]),
     "lgm_optim_scale": (_c_int, [_vp, _c_int, _vp, _c_ll, _vp, _vp, _vp]),
+    "lgm_mesh_density_workspace_size": (_c_size, [_c_ll, _c_int, _c_int, _c_int, _c_ll]),
+    "lgm_mesh_density_count": (_c_int, [_vp, _c_ll, _c_float, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_size,
+                                        _vp, _vp, _vp]),
+    "lgm_mesh_density": (_c_int, [_vp, _c_ll, _c_float, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _c_ll, _vp, _vp, _vp,
+                                  _c_size, _vp, _vp]),
+    "lgm_mesh_extract_workspace_size": (_c_size, [_c_int, _c_int, _c_int]),
+    "lgm_mesh_count": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, _vp, _c_size, _vp, _vp, _vp]),
+    "lgm_mesh_emit": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_size, _c_ll, _c_ll, _vp, _vp,
+                               _vp, _c_ll, _c_ll, _vp, _vp]),
     "lgm_profiler_create": (_vp, []),
     "lgm_profiler_summary": (_c_int, [_vp, ctypes.c_char_p, _c_size]),
     "lgm_profiler_reset": (_c_int, [_vp]),
@@ -108,7 +117,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN

@@ -324,6 +324,19 @@ class GaussianRenderer:
         data = torch.cat([means3D, f_dc, opacity, scales, rotations], dim=1).numpy().astype(np.float32)
         write_ply(path, names, data)
 
+    def save_mesh(self, gaussians, path, **kw):
+        """Additive (the reference's convert.py step): B == 1 as in save_ply; the Gaussians as a closed, coloured triangle
+        mesh (lgm_amd.mesh.gaussians_to_mesh, whose keywords `kw` are) written as .obj, or .ply by the path's
+        extension. Returns the Mesh."""
+        from .mesh import gaussians_to_mesh
+        assert gaussians.shape[0] == 1, "only support batch size 1"
+        mesh = gaussians_to_mesh(gaussians, **kw)
+        if str(path).lower().endswith(".ply"):
+            mesh.save_ply(path)
+        else:
+            mesh.save_obj(path)
+        return mesh
+
     def load_ply(self, path, compatible=True):
         """core/gs.py:154-190: returns a CPU [N,14] tensor."""
         props = read_ply(path)

@@ -6,9 +6,12 @@ and N orbit frames through lgm_amd.cameras.render_orbit_frames. Runs on the GPU 
 
     python scripts/lgm_infer.py [--png tests/golden/catstatue_rgba.png] [--ckpt STATE_DICT.pt] [--frames 8]
                                 [--device cuda|cpu] [--bf16] [--native-conv] [--out bench_out_lgm_infer]
+                                [--mesh] [--mesh-resolution 256] [--mesh-iso 0.5]
 
 --native-conv (with --bf16 on the GPU) runs the UNet's stride-1 convolutions on the HIP kernel (UNet.native_conv)
 instead of the library convolution: no first-call solver search.
+--mesh also writes object.obj next to the PLY (lgm_amd.mesh: the Gaussians' density on a grid, surface nets) and adds
+its vertex and face counts to the JSON line.
 """
 from __future__ import annotations
 
@@ -37,6 +40,9 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="run the model under bf16 autocast (GPU)")
     ap.add_argument("--native-conv", action="store_true",
                     help="the UNet's stride-1 convolutions on the HIP kernel (16-bit on the GPU: with --bf16)")
+    ap.add_argument("--mesh", action="store_true", help="also export a coloured triangle mesh (object.obj)")
+    ap.add_argument("--mesh-resolution", type=int, default=256)
+    ap.add_argument("--mesh-iso", type=float, default=0.5)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -76,6 +82,13 @@ def main():
         os.makedirs(a.out, exist_ok=True)
         ply = os.path.join(a.out, "catstatue.ply" if "catstatue" in a.png else "object.ply")
         model.gs.save_ply(gaussians, ply)
+        mesh_info = {}
+        if a.mesh:
+            t0 = time.perf_counter()
+            obj = os.path.join(a.out, "object.obj")
+            mesh = model.gs.save_mesh(gaussians.float(), obj, resolution=a.mesh_resolution, iso=a.mesh_iso)
+            t["mesh_s"] = time.perf_counter() - t0
+            mesh_info = {"mesh": obj, "mesh_vertices": int(mesh.vertices.shape[0]), "mesh_faces": int(mesh.faces.shape[0])}
         t0 = time.perf_counter()
         az = np.arange(a.frames, dtype=np.float64) * (360.0 / max(a.frames, 1))
         frames = render_orbit_frames(model.gs, gaussians, az, radius=opt.cam_radius).cpu().numpy()
@@ -84,7 +97,7 @@ def main():
         Image.fromarray(f).save(os.path.join(a.out, f"frame_{i:03d}.png"))
     print(json.dumps({"device": str(dev), "gaussians": list(gaussians.shape), "finite": bool(torch.isfinite(gaussians).all()),
                       "ply": ply, "ply_bytes": os.path.getsize(ply), "frames": list(frames.shape),
-                      "frame_mean": float(frames.mean()), "seconds": {k: round(v, 3) for k, v in t.items()}}))
+                      "frame_mean": float(frames.mean()), **mesh_info, "seconds": {k: round(v, 3) for k, v in t.items()}}))
 
 
 if __name__ == "__main__":
