@@ -118,6 +118,7 @@ _lib = None
 
 
 ABI_VERSION = 10
+DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # include/lgm_attn.h LGM_ATTN_F32 / _BF16 / _F16
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN

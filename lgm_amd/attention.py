@@ -21,13 +21,11 @@ import torch.nn as nn
 from . import _native as nat
 from .linear import linear as _linear16
 
-_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
 
 def _dtype_code(t: torch.Tensor) -> int:
-    if t.dtype not in _DTYPES:
+    if t.dtype not in nat.DTYPE_CODES:
         raise nat.NativeError(f"attention supports float32/bfloat16/float16, got {t.dtype}")
-    return _DTYPES[t.dtype]
+    return nat.DTYPE_CODES[t.dtype]
 
 
 class _PackedAttention(torch.autograd.Function):
@@ -264,7 +262,7 @@ class MVAttention(nn.Module):
         if BV % self.num_frames:
             raise ValueError(f"batch {BV} is not a multiple of num_frames={self.num_frames}")
         B = BV // self.num_frames
-        if self.fused and x.is_cuda and x.dtype in _DTYPES:
+        if self.fused and x.is_cuda and x.dtype in nat.DTYPE_CODES:
             # fused token layout kernels around the attention core (same math; GroupNorm in fp32 as under autocast)
             ac = _autocast_dtype("cuda")
             tok_dtype = ac if ac is not None else x.dtype

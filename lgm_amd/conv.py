@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 
-_CODES = {torch.bfloat16: 1, torch.float16: 2}  # include/lgm_attn.h LGM_ATTN_BF16 / LGM_ATTN_F16
+_CODES = (torch.bfloat16, torch.float16)  # the operand dtypes the kernels take (codes: nat.DTYPE_CODES)
 _GRID_MAX = 2 ** 31 - 1
 
 
@@ -34,14 +34,14 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, ksize: int, want_db: bool):
     L = nat.lib()
     ws_bytes = L.lgm_conv_wgrad_workspace_size(N, Cin, Cout, H, W, ksize, int(want_db))
     ws = torch.empty(max(ws_bytes, 1), device=dy.device, dtype=torch.uint8)
-    nat.check(L.lgm_conv_wgrad(_CODES[dy.dtype], N, Cin, Cout, H, W, ksize, nat.ptr(dy), nat.ptr(x), nat.ptr(dw),
+    nat.check(L.lgm_conv_wgrad(nat.DTYPE_CODES[dy.dtype], N, Cin, Cout, H, W, ksize, nat.ptr(dy), nat.ptr(x), nat.ptr(dw),
                                nat.ptr(db), nat.ptr(ws), ws_bytes, nat.stream_of(dy.device), nat.diag()),
               "lgm_conv_wgrad")
     return dw, db
 
 
 def _w_code(t: torch.Tensor, dt) -> int:
-    return 0 if t.dtype == torch.float32 else _CODES[dt]
+    return nat.DTYPE_CODES[torch.float32 if t.dtype == torch.float32 else dt]
 
 
 def conv_forward(x16: torch.Tensor, w: torch.Tensor, bias, ksize: int) -> torch.Tensor:
@@ -55,7 +55,7 @@ def conv_forward(x16: torch.Tensor, w: torch.Tensor, bias, ksize: int) -> torch.
     L = nat.lib()
     ws_bytes = L.lgm_conv_forward_workspace_size(N, Cin, Cout, H, W, ksize)
     ws = torch.empty(max(ws_bytes, 1), device=x16.device, dtype=torch.uint8)
-    nat.check(L.lgm_conv_forward(_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, nat.ptr(x16), nat.ptr(w),
+    nat.check(L.lgm_conv_forward(nat.DTYPE_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, nat.ptr(x16), nat.ptr(w),
                                  nat.ptr(bias), 0 if bias is None else _w_code(bias, dt), nat.ptr(y), nat.ptr(ws),
                                  ws_bytes, nat.stream_of(x16.device), nat.diag()), "lgm_conv_forward")
     return y
@@ -71,7 +71,7 @@ def conv_dgrad(dy16: torch.Tensor, w: torch.Tensor, ksize: int) -> torch.Tensor:
     L = nat.lib()
     ws_bytes = L.lgm_conv_dgrad_workspace_size(N, Cin, Cout, H, W, ksize)
     ws = torch.empty(max(ws_bytes, 1), device=dy16.device, dtype=torch.uint8)
-    nat.check(L.lgm_conv_dgrad(_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, nat.ptr(dy16), nat.ptr(w),
+    nat.check(L.lgm_conv_dgrad(nat.DTYPE_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, nat.ptr(dy16), nat.ptr(w),
                                nat.ptr(dx), nat.ptr(ws), ws_bytes, nat.stream_of(dy16.device), nat.diag()),
               "lgm_conv_dgrad")
     return dx

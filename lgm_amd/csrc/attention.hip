@@ -33,18 +33,14 @@
 
 #include <type_traits>
 
+#include "cdna4.h"
 #include "common.h"
-#include "lgm_attn.h"
 
 namespace lgm {
 namespace attn {
 
 // ------------------------------------------------------------------------------------------------------------
-// shared types and fragments
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
+// shared types and fragments (the vector types, the 16-bit MFMA, LDS DMA and the transposing read: cdna4.h)
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 constexpr int BQ = 64, BK = 64, NT = 256;  // 4 wavefronts x 16 rows
@@ -367,11 +363,6 @@ int bwd_f32(int B, int L, int H, float scale, const void *q, const void *k, cons
 
 // ------------------------------------------------------------------------------------------------------------
 // 16-bit path (bf16, fp16): k_attn_fwd2 | k_attn_dq2, k_attn_dkdv2.
-template <int DT> __device__ __forceinline__ f32x4 mfma32(typename Ty<DT>::V8 a, typename Ty<DT>::V8 b, f32x4 c) {
-    if constexpr (DT == LGM_ATTN_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 // forward (v2): grid (ceil(L / (64 QS)), B*H), block 256; wavefront w owns 16 QS query rows.
 //   * S^T = K Q^T per 16-key sub-tile: the K fragment (ds_read_b128 from the row-major tile) is read once and used
 //     for all QS query sub-tiles held in registers;
@@ -403,13 +394,7 @@ __device__ __forceinline__ typename Ty<DT>::V8 tr_frag(const typename Ty<DT>::T 
     using V8 = typename Ty<DT>::V8;
     const int g = lane >> 4, i = lane & 15;
     const T *p0 = tile + (k0 + 4 * g + (i >> 2)) * ld + d0 + 4 * (i & 3);
-    typedef short s4v __attribute__((__vector_size__(8)));
-    // the transposing read moves 16-bit elements regardless of type: the i16 form serves bf16 and f16
-    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v *)(p0));
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v *)(p0 + 16 * ld));
-    typedef __attribute__((ext_vector_type(8))) short s8v;
-    const s8v r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(V8, r);
+    return __builtin_bit_cast(V8, tr16_pair(p0, p0 + 16 * ld));
 }
 
 // K/V tiles staged by LDS DMA (global_load_lds_dwordx4: lane i's 16 B land at M0 + 16 i, no VGPR staging) at
@@ -425,31 +410,6 @@ template <int D>
 __device__ __forceinline__ int kv_swz(int r) {
     if constexpr (D == 32) return ((r >> 2) & 1) << 1;       // rows r, r + 4 of a transposed read: other 32 B
     else return (((r >> 1) & 3) << 1) | ((r >> 2) & 1);       // D = 64: two rows per 256-B bank line
-}
-__device__ __forceinline__ unsigned lds_addr32(const void *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-// Issued from inline asm so that the compiler's waitcnt pass does not tie later LDS reads to the pending copy;
-// completion is ordered by vm_wait() + a barrier. M0 is saved and restored (the compiler owns it).
-__device__ __forceinline__ void lds_dma16(const void *src, unsigned lds_base) {
-    const unsigned m = __builtin_amdgcn_readfirstlane(lds_base);
-    unsigned saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(saved)
-                 : "s"(m), "v"(src)
-                 : "memory");
-}
-__device__ __forceinline__ void vm_wait() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0)
-// The 4-byte form: lane i's dword lands at M0 + 4 i (64 consecutive floats per wave-instruction).
-__device__ __forceinline__ void lds_dma4(const void *src, unsigned lds_base) {
-    const unsigned m = __builtin_amdgcn_readfirstlane(lds_base);
-    unsigned saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(saved)
-                 : "s"(m), "v"(src)
-                 : "memory");
 }
 // Per-row constants the dK,dV pass needs, written by k_attn_dq2 (16-bit paths): -lse * log2(e) and -delta of every
 // query row, [B*H][Lp] each (Lp = L rounded up to 64; rows >= L hold -inf and 0, so P = 0 there), DMA'd with each
@@ -469,8 +429,8 @@ __device__ __forceinline__ void dma_tiles(const T *pa, long long lda, const T *p
         const int slot = w * 16 * CPR + j * 64 + lane;  // 16-B slot of the image this lane fills
         const int r = slot / CPR, c = (slot % CPR) ^ kv_swz<D>(r);
         const long long row = min(r0 + r, L - 1);
-        lds_dma16(pa + row * lda + 8 * c, lds_addr32(ta) + 1024u * (w * (D / 32) + j));
-        lds_dma16(pb + row * ldb + 8 * c, lds_addr32(tb) + 1024u * (w * (D / 32) + j));
+        lds_dma<16>(pa + row * lda + 8 * c, lds_offset(ta) + 1024u * (w * (D / 32) + j));
+        lds_dma<16>(pb + row * ldb + 8 * c, lds_offset(tb) + 1024u * (w * (D / 32) + j));
     }
 }
 // dma_tiles for a tile loop: this lane's source offsets inside tile 0 are computed once; a full tile adds the
@@ -494,8 +454,8 @@ struct DmaStream {
             constexpr int RPP = 512 / D;  // rows per 1-KiB piece
 #pragma unroll
             for (int j = 0; j < D / 32; j++) {
-                lds_dma16(pa + (r0 + j * RPP) * lda + oa, lds_addr32(ta) + 1024u * (w * (D / 32) + j));
-                lds_dma16(pb + (r0 + j * RPP) * ldb + ob, lds_addr32(tb) + 1024u * (w * (D / 32) + j));
+                lds_dma<16>(pa + (r0 + j * RPP) * lda + oa, lds_offset(ta) + 1024u * (w * (D / 32) + j));
+                lds_dma<16>(pb + (r0 + j * RPP) * ldb + ob, lds_offset(tb) + 1024u * (w * (D / 32) + j));
             }
         } else {
             dma_tiles<D>(pa, lda, pb, ldb, r0, L, ta, tb);
@@ -515,12 +475,7 @@ __device__ __forceinline__ typename Ty<DT>::V8 tr_frag_swz(const typename Ty<DT>
     const int g = lane >> 4, i = lane & 15;
     const int row = k0 + 4 * g + (i >> 2), ch = (d0 >> 3) + ((i & 3) >> 1);
     const T *p0 = tile + row * D + 8 * (ch ^ kv_swz<D>(row)) + 4 * (i & 1);
-    typedef short s4v __attribute__((__vector_size__(8)));
-    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v *)(p0));
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v *)(p0 + 16 * D));
-    typedef __attribute__((ext_vector_type(8))) short s8v;
-    const s8v r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(V8, r);
+    return __builtin_bit_cast(V8, tr16_pair(p0, p0 + 16 * D));
 }
 
 // Waves per SIMD the compiler is held to (register cap 512 / n) for D <= 64; D = 128 stays at the compiler's
@@ -669,7 +624,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D == 32 && Q
             for (int s = 0; s < QS; s++) {
                 f32x4 a = {-m[s], -m[s], -m[s], -m[s]};  // the MFMA leaves exp2's argument itself
 #pragma unroll
-                for (int cc = 0; cc < D / 32; cc++) a = mfma32<DT>(kf[cc], qf[s].v[cc], a);
+                for (int cc = 0; cc < D / 32; cc++) a = mfma16<DT>(kf[cc], qf[s].v[cc], a);
                 sacc[s][sub] = a;
             }
         }
@@ -715,7 +670,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D == 32 && Q
                     pb[s][t][4 + i] = (T)__builtin_amdgcn_exp2f(sacc[s][2 * t + 1][i]);
                 }
 #pragma unroll
-            for (int t = 0; t < 2; t++) lacc[s] = mfma32<DT>(ones, pb[s][t], lacc[s]);
+            for (int t = 0; t < 2; t++) lacc[s] = mfma16<DT>(ones, pb[s][t], lacc[s]);
         }
         // ---- O^T += V^T P
 #pragma unroll
@@ -724,7 +679,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D == 32 && Q
             for (int dt = 0; dt < D / 16; dt++) {
                 const V8 vf = DMA ? tr_frag_swz<DT, D>(Vt, 32 * t, 16 * dt, lane) : tr_frag<DT>(Vt, LDK, 32 * t, 16 * dt, lane);
 #pragma unroll
-                for (int s = 0; s < QS; s++) oacc[s][dt] = mfma32<DT>(vf, pb[s][t], oacc[s][dt]);
+                for (int s = 0; s < QS; s++) oacc[s][dt] = mfma16<DT>(vf, pb[s][t], oacc[s][dt]);
             }
         if (more) {
             if constexpr (DMA) vm_wait();  // this wave's copy landed (the barrier publishes every wave's)
@@ -820,8 +775,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D <= 32 ? DK
         else
             ld_.load(qc + (long long)bh * L * D, D, dout + obase, (long long)H * D, qb, L);
         if (w == 0) {  // the tile's -lse' and -delta rows, straight into their LDS slots (workgroup-uniform by wave)
-            lds_dma4(nl2 + qb, lds_addr32(&sl[buf][0]));
-            lds_dma4(nd + qb, lds_addr32(&sd[buf][0]));
+            lds_dma<4>(nl2 + qb, lds_offset(&sl[buf][0]));
+            lds_dma<4>(nd + qb, lds_offset(&sd[buf][0]));
         }
     };
     auto store_rows2 = [&](int buf) {
@@ -874,8 +829,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D <= 32 ? DK
                     f32x4 a = ainit, dp = dinit;
 #pragma unroll
                     for (int cc = 0; cc < D / 32; cc++) {
-                        a = mfma32<DT>(qr[cc], kf[s].v[cc], a);     // S[q = 16 sub + 4g + i][key]
-                        dp = mfma32<DT>(orr[cc], vf[s].v[cc], dp);  // dP[q][key]
+                        a = mfma16<DT>(qr[cc], kf[s].v[cc], a);     // S[q = 16 sub + 4g + i][key]
+                        dp = mfma16<DT>(orr[cc], vf[s].v[cc], dp);  // dP[q][key]
                     }
                     sacc[s][h2] = a;
                     dpa[s][h2] = dp;
@@ -898,8 +853,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D <= 32 ? DK
                 const V8 qT = DMA ? tr_frag_swz<DT, D>(Qt, 32 * t, 16 * dt, lane) : tr_frag<DT>(Qt, LDK, 32 * t, 16 * dt, lane);  // Q^T
 #pragma unroll
                 for (int s = 0; s < KS; s++) {
-                    dva[s][dt] = mfma32<DT>(oT, pb[s], dva[s][dt]);
-                    dka[s][dt] = mfma32<DT>(qT, db[s], dka[s][dt]);
+                    dva[s][dt] = mfma16<DT>(oT, pb[s], dva[s][dt]);
+                    dka[s][dt] = mfma16<DT>(qT, db[s], dka[s][dt]);
                 }
             }
         }
@@ -1037,8 +992,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D <= 64 ? BW
                     f32x4 dp = {-dl[s], -dl[s], -dl[s], -dl[s]};
 #pragma unroll
                     for (int cc = 0; cc < D / 32; cc++) {
-                        a = mfma32<DT>(kr[cc], qf[s].v[cc], a);    // S^T[key = 16 sub + 4g + i][q]
-                        dp = mfma32<DT>(vr[cc], of[s].v[cc], dp);  // dP^T[key][q]
+                        a = mfma16<DT>(kr[cc], qf[s].v[cc], a);    // S^T[key = 16 sub + 4g + i][q]
+                        dp = mfma16<DT>(vr[cc], of[s].v[cc], dp);  // dP^T[key][q]
                     }
                     sacc[s][h2] = a;
                     dpa[s][h2] = dp;
@@ -1060,7 +1015,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(D <= 64 ? BW
             for (int dt = 0; dt < D / 16; dt++) {
                 const V8 kT = DMA ? tr_frag_swz<DT, D>(Kt, 32 * t, 16 * dt, lane) : tr_frag<DT>(Kt, LDK, 32 * t, 16 * dt, lane);  // K^T
 #pragma unroll
-                for (int s = 0; s < QS; s++) dqa[s][dt] = mfma32<DT>(kT, db[s], dqa[s][dt]);
+                for (int s = 0; s < QS; s++) dqa[s][dt] = mfma16<DT>(kT, db[s], dqa[s][dt]);
             }
         }
         if (more) {

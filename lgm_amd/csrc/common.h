@@ -12,6 +12,12 @@ namespace lgm {
 void set_error(const char *fmt, ...);
 void clear_error();
 
+// Argument checks of the 16-bit MFMA entry points (`who`: the entry point's name). Each returns LGM_OK, or sets the
+// error and returns its code: LGM_E_INVALID unless dtype is LGM_ATTN_BF16 or LGM_ATTN_F16; LGM_E_WORKSPACE where
+// `need` bytes are wanted and the caller's `have` bytes at `ws` are fewer (or ws is NULL).
+int check_dtype16(const char *who, int dtype);
+int check_workspace(const char *who, const void *ws, size_t have, size_t need);
+
 // The diagnostics of the entry point running on this thread: set for the duration of one call by a DiagScope at
 // its top (entry points run synchronously on the caller's thread and enqueue everything before returning), so
 // nothing outlives the call.

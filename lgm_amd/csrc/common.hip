@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "lgm_attn.h"
 #include "lgm_common.h"
 
 struct lgm_profiler {
@@ -40,6 +41,17 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 void clear_error() { g_err[0] = 0; }
+
+int check_dtype16(const char *who, int dtype) {
+    if (dtype == LGM_ATTN_BF16 || dtype == LGM_ATTN_F16) return LGM_OK;
+    set_error("%s: dtype must be bf16 or fp16 (got %d)", who, dtype);
+    return LGM_E_INVALID;
+}
+int check_workspace(const char *who, const void *ws, size_t have, size_t need) {
+    if (have >= need && (!need || ws)) return LGM_OK;
+    set_error("%s: workspace too small (%zu < %zu bytes)", who, ws ? have : 0, need);
+    return LGM_E_WORKSPACE;
+}
 
 static thread_local int g_scope_depth = 0;
 DiagScope::DiagScope(const lgm_diag *d) {

@@ -24,18 +24,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cdna4.h"
 #include "common.h"
-#include "lgm_attn.h"
 #include "lgm_conv.h"
 
 namespace lgm {
 namespace cf {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr int BM = 64;             // output channels of one workgroup (2 waves x 2 fragments of 16)
 constexpr int BN = 128;            // slots of one workgroup (2 waves x 4 fragments of 16)
@@ -46,15 +40,6 @@ constexpr int GS = 4 * FS;         // chunks per channel group: a multiple of 16
 constexpr int SLOTS = 512;         // workgroup slots of the chip (2 per CU at 3 x 3)
 constexpr int MIN_STEPS = 4;       // K steps per split at least
 constexpr int MAX_SPLIT = 16;
-
-template <int DT> __device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (DT == LGM_ATTN_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                       0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                      0);
-}
 
 // fp32 -> the 16-bit type, round to nearest even (as tensor.to(dt))
 template <int DT> __device__ __forceinline__ unsigned rnd(float v) {
@@ -134,7 +119,7 @@ template <int KS> struct Pre {
 };
 
 // k_conv: grid (tiles * S), block 256. Workgroup -> (split s, pixel tile pt, channel tile mt); split s covers the K
-// steps [s q + min(s, r), ...) of the KCN steps (q, r = divmod(KCN, S)). S == 1 writes out (bias added, one rounding);
+// steps of its split_range (work_split.h) of the KCN steps. S == 1 writes out (bias added, one rounding);
 // S > 1 writes the fp32 partial of split s at the output's own element offsets.
 template <int DT, int KS>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) void k_conv(
@@ -147,8 +132,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
     const int s = blockIdx.x / tiles, tile = blockIdx.x - s * tiles, pt = tile / MT, mt = tile - pt * MT;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, wm = w >> 1, wn = w & 1;
     const int g = lane >> 4, i = lane & 15;
-    const int q = KCN / S, r = KCN - q * S;
-    const int kc0 = s * q + (s < r ? s : r), nk = q + (s < r ? 1 : 0);
+    int kc0, nk;
+    split_range(KCN, S, s, kc0, nk);
     const int H = G.H, W = G.W, Wp = G.Wp, Ci = G.Ci;
     const long long HW = G.HW;
 
@@ -251,7 +236,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
 #pragma unroll
                 for (int f = 0; f < 4; f++)
 #pragma unroll
-                    for (int a = 0; a < 2; a++) acc[a][f] = mfma<DT>(fa[a], bf[f + kx], acc[a][f]);
+                    for (int a = 0; a < 2; a++) acc[a][f] = mfma16<DT>(fa[a], bf[f + kx], acc[a][f]);
             }
         }
         __syncthreads();  // every wave has read the step: the images are free
@@ -395,10 +380,7 @@ int run(const char *who, bool dgrad, int dtype, int wdt, int N, int Cin, int Cou
         const lgm_diag *diag) {
     lgm::clear_error();
     lgm::DiagScope ds(diag);
-    if (dtype != LGM_ATTN_BF16 && dtype != LGM_ATTN_F16) {
-        lgm::set_error("%s: dtype must be bf16 or fp16 (got %d)", who, dtype);
-        return LGM_E_INVALID;
-    }
+    if (int rc = lgm::check_dtype16(who, dtype)) return rc;
     if (wdt != LGM_ATTN_F32 && wdt != dtype) {
         lgm::set_error("%s: weight dtype must be fp32 or the operand dtype %d (got %d)", who, dtype, wdt);
         return LGM_E_INVALID;
@@ -427,10 +409,7 @@ int run(const char *who, bool dgrad, int dtype, int wdt, int N, int Cin, int Cou
         return LGM_E_INVALID;
     }
     const size_t need = ws_size(N, Ci, Co, H, W, ksize);
-    if (workspace_bytes < need || (need && !workspace)) {
-        lgm::set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace ? workspace_bytes : 0, need);
-        return LGM_E_WORKSPACE;
-    }
+    if (int rc = lgm::check_workspace(who, workspace, workspace_bytes, need)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == LGM_ATTN_BF16)
         return run_t<LGM_ATTN_BF16>(who, dgrad, wdt, N, Cin, Cout, H, W, ksize, x, w, bias, bdt, y, workspace, P, st);

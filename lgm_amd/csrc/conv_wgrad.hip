@@ -22,17 +22,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cdna4.h"
 #include "common.h"
-#include "lgm_attn.h"
 #include "lgm_conv.h"
 
 namespace lgm {
 namespace cw {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int BM = 64, BN = 64;    // output tile (Cout x Cin) of one workgroup
 constexpr int BK = 64;             // slots per stage: two 32-slot MFMA K steps
@@ -46,25 +41,6 @@ constexpr int SLOTS_1 = 256 * 4;   // at 1 x 1 (98 VGPRs, 16 KB of LDS: 4 per CU
 constexpr int MIN_STAGES = 8;      // stages per split at least
 constexpr int MAX_ROUNDS = 4;      // rounds of SLOTS workgroups at most (where the tiles alone are not more)
 constexpr int DBT = 8;             // k_conv_wgrad_reduce lanes per bias-gradient row
-
-template <int DT> struct Op;
-template <> struct Op<LGM_ATTN_BF16> { using V8 = bf16x8; static constexpr unsigned ONE2 = 0x3f803f80u; };
-template <> struct Op<LGM_ATTN_F16> { using V8 = f16x8; static constexpr unsigned ONE2 = 0x3c003c00u; };
-
-template <int DT> __device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    using V8 = typename Op<DT>::V8;
-    if constexpr (DT == LGM_ATTN_BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(V8, a), __builtin_bit_cast(V8, b), c, 0, 0, 0);
-}
-
-// XCD-grouped work order (wgrad.hip xcd_item): the workgroups of one XCD take a contiguous range of the (split, tile)
-// items, so the tiles that read the same dy / x strips share an L2.
-__device__ __forceinline__ int xcd_item(int b, int M) {
-    const int q = M >> 3, r = M & 7, g = b & 7, i = b >> 3;
-    return (g < r ? g * (q + 1) : r * (q + 1) + (g - r) * q) + i;
-}
 
 struct Geo {
     int N, Cin, Cout, H, W, Wp;
@@ -89,8 +65,9 @@ template <int KS> struct Pre {
     unsigned side[KS][2];
 };
 
-// k_conv_wgrad: grid (tiles * S), block 256. Workgroup -> (split s, tile (mt, nt)); split s covers the stages
-// [s q + min(s, r), ...) of the nst_all stages (q, r = divmod(nst_all, S)).
+// k_conv_wgrad: grid (tiles * S), block 256. Workgroup item xcd_item(blockIdx) (work_split.h) -> (split s, tile
+// (mt, nt)): the workgroups of one XCD take a contiguous range of the items, so the tiles that read the same dy / x
+// strips share an L2. Split s covers its split_range of the nst_all stages.
 template <int DT, int KS>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) void k_conv_wgrad(
     Geo G, const uint16_t *__restrict__ dy, const uint16_t *__restrict__ x, int S, int NT, long long nst_all,
@@ -106,9 +83,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) 
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, wm = w >> 1, wn = w & 1;
     const int wn_u = __builtin_amdgcn_readfirstlane(w) & 1;
     const int g = lane >> 4, i = lane & 15;
-    const long long q = nst_all / S, r = nst_all - q * S;
-    const long long st0 = s * q + (s < r ? s : r);
-    const int nst = (int)(q + (s < r ? 1 : 0));
+    long long st0, nst_ll;
+    split_range(nst_all, S, s, st0, nst_ll);
+    const int nst = (int)nst_ll;
     const bool want_db = dbpart != nullptr && nt == 0 && wn_u == 0;
     const int H = G.H, W = G.W, Wp = G.Wp;
 
@@ -186,7 +163,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #pragma unroll
     for (int f = 0; f < 4 * TAPS; f++) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
     dbacc[0] = dbacc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const u32x4 ones = u32x4{Op<DT>::ONE2, Op<DT>::ONE2, Op<DT>::ONE2, Op<DT>::ONE2};
+    const u32x4 ones = u32x4{Op16<DT>::ONE2, Op16<DT>::ONE2, Op16<DT>::ONE2, Op16<DT>::ONE2};
 
     Pre<KS> P;
     if (nst > 0) P = load();
@@ -201,8 +178,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #pragma unroll
             for (int a = 0; a < 2; a++) fa[a] = *reinterpret_cast<const u32x4 *>(sA + chunk(kgr, 32 * wm + 16 * a + i));
             if (want_db) {
-                dbacc[0] = mfma<DT>(fa[0], ones, dbacc[0]);
-                dbacc[1] = mfma<DT>(fa[1], ones, dbacc[1]);
+                dbacc[0] = mfma16<DT>(fa[0], ones, dbacc[0]);
+                dbacc[1] = mfma16<DT>(fa[1], ones, dbacc[1]);
             }
 #pragma unroll
             for (int b = 0; b < 2; b++) {
@@ -220,13 +197,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #pragma unroll
                         for (int a = 0; a < 2; a++) {
                             const int t = (a * 2 + b) * TAPS + ky * 3;
-                            acc[t] = mfma<DT>(fa[a], vl, acc[t]);
-                            acc[t + 1] = mfma<DT>(fa[a], v, acc[t + 1]);
-                            acc[t + 2] = mfma<DT>(fa[a], vr, acc[t + 2]);
+                            acc[t] = mfma16<DT>(fa[a], vl, acc[t]);
+                            acc[t + 1] = mfma16<DT>(fa[a], v, acc[t + 1]);
+                            acc[t + 2] = mfma16<DT>(fa[a], vr, acc[t + 2]);
                         }
                     } else {
 #pragma unroll
-                        for (int a = 0; a < 2; a++) acc[a * 2 + b] = mfma<DT>(fa[a], v, acc[a * 2 + b]);
+                        for (int a = 0; a < 2; a++) acc[a * 2 + b] = mfma16<DT>(fa[a], v, acc[a * 2 + b]);
                     }
                 }
             }
@@ -353,10 +330,7 @@ extern "C" int lgm_conv_wgrad(int dtype, int N, int Cin, int Cout, int H, int W,
     using namespace lgm::cw;
     lgm::clear_error();
     lgm::DiagScope ds(diag);
-    if (dtype != LGM_ATTN_BF16 && dtype != LGM_ATTN_F16) {
-        lgm::set_error("lgm_conv_wgrad: dtype must be bf16 or fp16 (got %d)", dtype);
-        return LGM_E_INVALID;
-    }
+    if (int rc = lgm::check_dtype16("lgm_conv_wgrad", dtype)) return rc;
     if (ksize != 1 && ksize != 3) {
         lgm::set_error("lgm_conv_wgrad: ksize must be 1 or 3 (got %d)", ksize);
         return LGM_E_INVALID;
@@ -380,12 +354,9 @@ extern "C" int lgm_conv_wgrad(int dtype, int N, int Cin, int Cout, int H, int W,
         return LGM_E_INVALID;
     }
     const size_t need = lgm_conv_wgrad_workspace_size(N, Cin, Cout, H, W, ksize, db != nullptr);
-    if (workspace_bytes < need || (need && !workspace)) {
-        lgm::set_error("lgm_conv_wgrad: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : 0, need);
-        return LGM_E_WORKSPACE;
-    }
+    if (int rc = lgm::check_workspace("lgm_conv_wgrad", workspace, workspace_bytes, need)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    f32x4 *part = (f32x4 *)workspace;
+    lgm::f32x4 *part = (lgm::f32x4 *)workspace;
     float *dbpart = db && P.S ? (float *)((char *)workspace + ((P.part_bytes + 255) & ~(size_t)255)) : nullptr;
     if (P.S > 0) {
         Geo G;

@@ -8,6 +8,7 @@
 // some of its pixels pass upstream's `alpha >= 1/255` test. Per-pixel arithmetic, thresholds, the early
 // termination and the reverse recurrences are upstream's; alpha is v_exp_f32 of the pre-scaled quadratic form plus
 // log2(opacity) (the compositing records of render_common.h: 5 VALU + exp per (entry, pixel)).
+#include "cdna4.h"
 #include "render_common.h"
 
 #include <type_traits>
@@ -52,14 +53,11 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return v;
 }
 
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 constexpr int WU_LD = 68;  // row stride of the per-wave [16 columns][64 pixels] gradient image (16-B aligned rows)
 // Columns 4..11 of that image hold pixel p at p ^ 8 (WU_SWZ): with the 17-slot row stride this puts the 16 lanes of
 // every ds_read_b128 group of the batch reads (lanes {0-3, 12-15, 20-27}, ... : MI355X_MICROARCH.md §LDS) on 16
 // distinct 16-B slots; unswizzled, columns 10, 11 and 12, 13 of one group shared two slots (2-way).
 __device__ __forceinline__ int wu_swz(int col) { return (col >= 4 && col < 12) ? 8 : 0; }
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
 typedef __attribute__((ext_vector_type(2))) float f32x2v;
 constexpr int MB = 8;      // entries per moment-MFMA batch (columns 0..7: w, 8..15: u)
@@ -94,40 +92,8 @@ constexpr int BWD_CHUNK = 64;
 // backward lists are padded to MB with the sentinel: every list position is one MFMA batch column (k_render_bwd)
 using StageBwd = StageT<2, MB, BWD_CHUNK>;
 
-// Wait for every outstanding vector-memory operation of this wave (incl. its LDS DMA). A hard s_waitcnt: the
-// compiler's waitcnt pass sees it, and does not itself track LDS written by DMA.
-__device__ __forceinline__ void vm_wait_all() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0) only
-
-// LDS DMA (global_load_lds_dwordx{3,4}: lane i's bytes land at M0 + 16 i). Issued from inline asm on purpose:
-// the compiler's waitcnt pass treats any later LDS access that may alias a pending DMA as dependent on it and
-// would wait for the prefetch right after issuing it. Hidden from the pass, the DMA only makes the pass's own
-// vmcnt waits more conservative (still correct); its completion is ordered explicitly by vm_wait_all() plus a
-// barrier. M0 is saved and restored around it (the compiler owns M0), with the M0 -> LDS-DMA wait state.
-// The LDS address of a shared-memory pointer as a 32-bit offset (an address-space cast, not the 64-bit flat pointer:
-// kept live across the staging loop, the flat pointers were spilled and each reload's vmcnt(0) serialised the DMAs).
-__device__ __forceinline__ unsigned lds_offset(const void *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-template <int BYTES>
-__device__ __forceinline__ void lds_dma(const void *src, unsigned lds_row0) {
-    const unsigned m = __builtin_amdgcn_readfirstlane(lds_row0);
-    unsigned saved;
-    if (BYTES == 16)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(saved)
-                     : "s"(m), "v"(src)
-                     : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx3 %2, off\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(saved)
-                     : "s"(m), "v"(src)
-                     : "memory");
-}
-
-// Issue the LDS DMA of one entry (this lane's row of wave w's 64-row slice). Asynchronous: the rows are valid
-// after vm_wait_all() in every issuing wave followed by a barrier.
+// Issue the LDS DMA of one entry (this lane's row of wave w's 64-row slice; lds_dma, cdna4.h). Asynchronous: the
+// rows are valid after vm_wait() in every issuing wave followed by a barrier.
 template <class Buf>
 __device__ __forceinline__ void stage_dma(Buf &B, int w, unsigned gid, size_t gbase, int b, int N,
                                           const float4 *__restrict__ gP, const float4 *__restrict__ gQ,
@@ -276,7 +242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_F
         const int k = b0 + tid;
         StageBuf &B = S.buf[0];
         if (k < n) stage_dma(B, w, id_a, gbase, b, d.N, gP, gQ, gauss);
-        vm_wait_all();
+        vm_wait();
         stage_commit(S, B, tid, k < n, 0u, tx0, ty0, false);
         __syncthreads();
 #ifdef LGM_FWD_STAMPS
@@ -820,12 +786,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
     const int nlist = min(n, max(max(wl4.x, wl4.y), max(wl4.z, wl4.w)));
     const int s0 = (c * TILE_PIX) << d.ck_shift;
     if (s0 >= nlist) {  // workgroup-uniform (the early DMA must land before the workgroup retires)
-        vm_wait_all();
+        vm_wait();
         return;
     }
     const int s1 = (c + 1 <= nck[tile]) ? min(nlist, s0 + (TILE_PIX << d.ck_shift)) : nlist;
     if (s0 >= s1) {  // (nothing to do; likewise)
-        vm_wait_all();
+        vm_wait();
         return;
     }
     const unsigned long long t_item = d.counters ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -970,7 +936,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
     // word per chunk parity, and the next chunk's DMA overwrites the buffer of chunk c - 1, whose last reader (the
     // conversion of c - 1) finished before F of c - 1. Each wave zeroes its own moment slot at the top of a chunk,
     // after the conversion that read it (before F).
-    vm_wait_all();
+    vm_wait();
     __syncthreads();  // the first chunk's rows and the sentinel rows
     int cur = 0;
 #ifdef LGM_BWD_STAMPS
@@ -1161,7 +1127,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
         SEC_ADD(sec[4], ts_c2, ts_c3);  // barrier + moments -> partials
 #endif
         // the next chunk's DMA and ids have landed before the atomics below go out (they cannot delay it)
-        vm_wait_all();
+        vm_wait();
 #ifdef LGM_BWD_STAMPS
         SEC_T(ts_c3a);
         SEC_ADD(sec[5], ts_c3, ts_c3a);  // DMA wait (and any earlier outstanding vector-memory op of this wave)

@@ -21,18 +21,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cdna4.h"
 #include "common.h"
-#include "lgm_attn.h"
 #include "lgm_linear.h"
 
 namespace lgm {
 namespace wg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef short s4v __attribute__((__vector_size__(8)));
-typedef __attribute__((ext_vector_type(8))) short s8v;
 
 constexpr int BM = 128, BN = 128;  // output tile (dw rows x columns) of one workgroup
 // K rows per stage: two 32-row MFMA K steps per barrier, double-buffered (one stage in flight). Against 32-row stages in
@@ -51,32 +45,6 @@ constexpr int SLOTS = 256 * WPE;
 constexpr int FRAGS = 16;          // 16 x 16 accumulator blocks per wave
 constexpr int DBT = 8;             // k_wgrad_reduce lanes per bias-gradient row
 
-template <int DT> struct Op;
-template <> struct Op<LGM_ATTN_BF16> { using V8 = bf16x8; static constexpr short ONE = 0x3f80; };
-template <> struct Op<LGM_ATTN_F16> { using V8 = f16x8; static constexpr short ONE = 0x3c00; };
-
-template <int DT> __device__ __forceinline__ f32x4 mfma(typename Op<DT>::V8 a, typename Op<DT>::V8 b, f32x4 c) {
-    if constexpr (DT == LGM_ATTN_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ unsigned lds_addr32(const void *p) {
-    return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-// LDS DMA (global_load_lds_dwordx4: lane i's 16 B land at M0 + 16 i). Inline asm so that the compiler's waitcnt pass
-// does not tie later LDS reads to the pending copy; completion is ordered by the counted vmcnt waits + a barrier.
-__device__ __forceinline__ void lds_dma16(const void *src, unsigned lds_base) {
-    const unsigned m = __builtin_amdgcn_readfirstlane(lds_base);
-    unsigned saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(saved)
-                 : "s"(m), "v"(src)
-                 : "memory");
-}
-// s_waitcnt vmcnt(n) (n <= 15), leaving lgkmcnt / expcnt alone
-template <int n> __device__ __forceinline__ void vm_wait() { __builtin_amdgcn_s_waitcnt(0x0F70 | n); }
-
 // One operand's stage (rows k0 .. k0 + 31, columns col0 .. col0 + 127) into its swizzled image: wave w copies the
 // pieces 2w and 2w + 1 (4 rows of 256 B each). Columns past ncols read the last 16 B of the row (finite; only outputs
 // past M / N, which are never stored, see them). Rows past kend must be ZERO (they would add to valid outputs): the
@@ -92,7 +60,7 @@ __device__ __forceinline__ void stage(const uint16_t *__restrict__ src, long lon
         const int col = min(col0 + 16 * lc + 8 * (slot & 1), ncols - 8);
         const uint16_t *s = src + (long long)(k0 + row) * ld + col;
         if (!TAIL) {
-            lds_dma16(s, lds_addr32(img) + 1024u * p);
+            lds_dma<16>(s, lds_offset(img) + 1024u * p);
         } else {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (k0 + row < kend) v = *reinterpret_cast<const uint4 *>(s);
@@ -105,24 +73,15 @@ __device__ __forceinline__ void stage(const uint16_t *__restrict__ src, long lon
 // (g, i) receives column 16 c + i at rows 4g .. 4g + 3 and 16 + 4g .. 16 + 4g + 3 (the same row order for both
 // operands of a product, so the K sum is complete).
 template <int DT>
-__device__ __forceinline__ typename Op<DT>::V8 frag(const unsigned char *img, int c, int lane) {
+__device__ __forceinline__ typename Op16<DT>::V8 frag(const unsigned char *img, int c, int lane) {
     const int g = lane >> 4, i = lane & 15, r = 4 * g + (i >> 2);
     const unsigned char *p = img + r * 256 + ((c ^ (r & 7)) << 5) + 8 * (i & 3);  // (row r + 16: the same swizzle)
-    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v *)(p));
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v *)(p + 16 * 256));
-    const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(typename Op<DT>::V8, v);
+    return __builtin_bit_cast(typename Op16<DT>::V8, tr16_pair(p, p + 16 * 256));
 }
 
-// XCD-grouped work order (render_common.h xcd_item): the workgroups of one XCD take a contiguous range of the
-// (split, tile) items, i.e. mostly every tile of one K range, so the tiles that read the same dy / x rows share an L2.
-__device__ __forceinline__ int xcd_item(int b, int M) {
-    const int q = M >> 3, r = M & 7, g = b & 7, i = b >> 3;
-    return (g < r ? g * (q + 1) : r * (q + 1) + (g - r) * q) + i;
-}
-
-// k_wgrad: grid (tiles * S), block 256, 64 KB of LDS. Workgroup -> (split s, tile (mt, nt)); split s covers the
-// stages [s q + min(s, r), ...) of the ceil(K / 32) stages (q, r = divmod(stages, S)).
+// k_wgrad: grid (tiles * S), block 256, 64 KB of LDS. Workgroup item xcd_item(blockIdx) (work_split.h) -> (split s,
+// tile (mt, nt)): the workgroups of one XCD take mostly every tile of one K range, so the tiles that read the same
+// dy / x rows share an L2. Split s covers its split_range of the ceil(K / BK) stages.
 template <int DT>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) void k_wgrad(
     int K, int M, int N, const uint16_t *__restrict__ dy, long long ld_dy, const uint16_t *__restrict__ x,
@@ -135,12 +94,12 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) 
     const int m0 = mt * BM, n0 = nt * BN;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, wm = w >> 1, wn = w & 1;
     const int wn_u = __builtin_amdgcn_readfirstlane(w) & 1;  // (wave-uniform copy of wn: a scalar branch)
-    const int nst_all = (K + BK - 1) / BK, q = nst_all / S, r = nst_all - q * S;
-    const int st0 = s * q + min(s, r), nst = q + (s < r ? 1 : 0);
+    int st0, nst;
+    split_range((K + BK - 1) / BK, S, s, st0, nst);
     const bool want_db = dbpart != nullptr;
-    using V8 = typename Op<DT>::V8;
-    const s8v ones_s = {Op<DT>::ONE, Op<DT>::ONE, Op<DT>::ONE, Op<DT>::ONE,
-                        Op<DT>::ONE, Op<DT>::ONE, Op<DT>::ONE, Op<DT>::ONE};
+    using V8 = typename Op16<DT>::V8;
+    constexpr short ONE = Op16<DT>::ONE;
+    const s8v ones_s = {ONE, ONE, ONE, ONE, ONE, ONE, ONE, ONE};
     const V8 ones = __builtin_bit_cast(V8, ones_s);
 
     f32x4 acc[FRAGS], dbacc[2];
@@ -184,17 +143,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) 
 #pragma unroll
             for (int u = 0; u < 4; u++)
 #pragma unroll
-                for (int v = 0; v < 4; v++) acc[4 * u + v] = mfma<DT>(fa[u], fb[v], acc[4 * u + v]);
+                for (int v = 0; v < 4; v++) acc[4 * u + v] = mfma16<DT>(fa[u], fb[v], acc[4 * u + v]);
             // (static fragment indices under a wave-uniform branch: indexing fa by 2 * wn, a VGPR value to the
             // compiler, became a ~1,500-instruction select chain per stage and doubled the launch: 30 -> 60 us at the
             // proj level)
             if (want_db && ((st0 + j) * (BK / 32) + kk) % NT == nt) {
                 if (wn_u == 0) {
-                    dbacc[0] = mfma<DT>(fa[0], ones, dbacc[0]);
-                    dbacc[1] = mfma<DT>(fa[1], ones, dbacc[1]);
+                    dbacc[0] = mfma16<DT>(fa[0], ones, dbacc[0]);
+                    dbacc[1] = mfma16<DT>(fa[1], ones, dbacc[1]);
                 } else {
-                    dbacc[0] = mfma<DT>(fa[2], ones, dbacc[0]);
-                    dbacc[1] = mfma<DT>(fa[3], ones, dbacc[1]);
+                    dbacc[0] = mfma16<DT>(fa[2], ones, dbacc[0]);
+                    dbacc[1] = mfma16<DT>(fa[3], ones, dbacc[1]);
                 }
             }
         }
@@ -294,10 +253,7 @@ extern "C" int lgm_linear_wgrad(int dtype, int K, int M, int N, const void *dy, 
     using namespace lgm::wg;
     lgm::clear_error();
     lgm::DiagScope ds(diag);
-    if (dtype != LGM_ATTN_BF16 && dtype != LGM_ATTN_F16) {
-        lgm::set_error("lgm_linear_wgrad: dtype must be bf16 or fp16 (got %d)", dtype);
-        return LGM_E_INVALID;
-    }
+    if (int rc = lgm::check_dtype16("lgm_linear_wgrad", dtype)) return rc;
     if (K < 0 || M <= 0 || N <= 0 || M % 8 || N % 8 || ld_dy < M || ld_x < N || ld_dy % 8 || ld_x % 8) {
         lgm::set_error("lgm_linear_wgrad: bad shape K=%d M=%d N=%d ld_dy=%lld ld_x=%lld (M, N, ld multiples of 8)", K,
                        M, N, ld_dy, ld_x);
@@ -311,13 +267,12 @@ extern "C" int lgm_linear_wgrad(int dtype, int K, int M, int N, const void *dy, 
         lgm::set_error("lgm_linear_wgrad: dy and x must be 16-byte aligned");
         return LGM_E_INVALID;
     }
-    if (workspace_bytes < lgm_linear_wgrad_workspace_size(K, M, N, db != nullptr)) {
-        lgm::set_error("lgm_linear_wgrad: workspace too small");
-        return LGM_E_WORKSPACE;
-    }
+    if (int rc = lgm::check_workspace("lgm_linear_wgrad", workspace, workspace_bytes,
+                                      lgm_linear_wgrad_workspace_size(K, M, N, db != nullptr)))
+        return rc;
     const Plan P = plan(K, M, N, db != nullptr);
     hipStream_t st = (hipStream_t)stream;
-    f32x4 *part = (f32x4 *)workspace;
+    lgm::f32x4 *part = (lgm::f32x4 *)workspace;
     float *dbpart = db ? (float *)((char *)workspace + ((P.part_bytes + 255) & ~(size_t)255)) : nullptr;
     const int grid = P.tiles * P.S;
     if (dtype == LGM_ATTN_BF16)

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import _native as nat
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = (torch.float32, torch.bfloat16)  # the input dtypes the kernels take (codes: nat.DTYPE_CODES)
 
 
 class _Head(torch.autograd.Function):
@@ -41,7 +41,7 @@ class _Head(torch.autograd.Function):
         L = nat.lib()
         ws_bytes = L.lgm_gaussian_head_workspace_size(B, V, h, w)
         ws = torch.empty(max(ws_bytes, 1), device=x.device, dtype=torch.uint8)
-        nat.check(L.lgm_gaussian_head_forward(_DT[x.dtype], B, V, h, w, nat.ptr(x), nat.ptr(W), nat.ptr(b),
+        nat.check(L.lgm_gaussian_head_forward(nat.DTYPE_CODES[x.dtype], B, V, h, w, nat.ptr(x), nat.ptr(W), nat.ptr(b),
                                               nat.ptr(out), nat.ptr(rot_norm), nat.ptr(ws), ws_bytes,
                                               nat.stream_of(x.device), nat.diag()), "lgm_gaussian_head_forward")
         ctx.save_for_backward(x, W, b if b is not None else W.new_empty(0), rot_norm)
@@ -59,7 +59,7 @@ class _Head(torch.autograd.Function):
         db = torch.empty(14, device=x.device, dtype=torch.float32) if has_bias else None
         ws_bytes = L.lgm_gaussian_head_workspace_size(B, V, h, w)
         ws = torch.empty(max(ws_bytes, 1), device=x.device, dtype=torch.uint8)
-        nat.check(L.lgm_gaussian_head_backward(_DT[x.dtype], B, V, h, w, nat.ptr(x), nat.ptr(W),
+        nat.check(L.lgm_gaussian_head_backward(nat.DTYPE_CODES[x.dtype], B, V, h, w, nat.ptr(x), nat.ptr(W),
                                                nat.ptr(b) if has_bias else None, nat.ptr(rot_norm), nat.ptr(d_out),
                                                nat.ptr(dx),
                                                nat.ptr(dW), nat.ptr(db), nat.ptr(ws), ws_bytes,

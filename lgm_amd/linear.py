@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 
-_CODES = {torch.bfloat16: 1, torch.float16: 2}  # include/lgm_attn.h LGM_ATTN_BF16 / LGM_ATTN_F16
+_CODES = (torch.bfloat16, torch.float16)  # the operand dtypes the kernel takes (codes: nat.DTYPE_CODES)
 
 
 class _Linear16(torch.autograd.Function):
@@ -48,7 +48,7 @@ class _Linear16(torch.autograd.Function):
             L = nat.lib()
             ws_bytes = L.lgm_linear_wgrad_workspace_size(K, M, N, int(want_b))
             ws = torch.empty(max(ws_bytes, 1), device=g.device, dtype=torch.uint8)
-            nat.check(L.lgm_linear_wgrad(_CODES[dt], K, M, N, nat.ptr(g2), M, nat.ptr(x2), N, nat.ptr(dw), nat.ptr(db),
+            nat.check(L.lgm_linear_wgrad(nat.DTYPE_CODES[dt], K, M, N, nat.ptr(g2), M, nat.ptr(x2), N, nat.ptr(dw), nat.ptr(db),
                                          nat.ptr(ws), ws_bytes, nat.stream_of(g.device), nat.diag()),
                       "lgm_linear_wgrad")
             dw = dw.to(wdt) if want_w else None

@@ -29,7 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
-from .attention import _DTYPES, _autocast_dtype
+from ._native import DTYPE_CODES as _DTYPES
+from .attention import _autocast_dtype
 from .unet import _raw_stream
 
 # torchvision's vgg16().features: (index, in, out) of the convolutions; a ReLU follows each; max-pools at POOLS

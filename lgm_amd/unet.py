@@ -23,7 +23,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
-from .attention import _DTYPES, MemEffAttention, MVAttention, _autocast_dtype
+from ._native import DTYPE_CODES as _DTYPES
+from .attention import MemEffAttention, MVAttention, _autocast_dtype
 from .conv import conv2d, conv2d_native
 from .cpu import attention_cpu
 

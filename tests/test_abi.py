@@ -83,6 +83,23 @@ def test_deterministic_flush_bound():
     assert L.lgm_render_det_flush_limit_log2(0, 16, 0) < 0
 
 
+def test_hardware_idioms_have_one_definition():
+    """The LDS-DMA statement, the transposing LDS read, the counted vmcnt wait and the 16-bit MFMA are written once,
+    in csrc/cdna4.h, and xcd_item once, in csrc/work_split.h: a fix to the M0 handling or to the wait encoding must
+    not miss a private copy in a kernel file."""
+    csrc = os.path.join(ROOT, "lgm_amd", "csrc")
+    code = {}
+    for src in glob.glob(os.path.join(csrc, "*")):
+        code[os.path.basename(src)] = "\n".join(line.split("//")[0] for line in open(src))  # (no comments)
+    mfma_files = ("conv_fwd.hip", "conv_wgrad.hip", "wgrad.hip", "attention.hip")
+    for needle, where in (("global_load_lds", code), ("ds_read_tr16", code), ("__builtin_amdgcn_s_waitcnt", code),
+                          ("__builtin_amdgcn_mfma_f32_16x16x32_", mfma_files)):
+        assert needle in code["cdna4.h"], needle
+        assert not [f for f in where if needle in code[f] and f != "cdna4.h"], needle
+    defs = [f for f, txt in code.items() if re.search(r"\bint\s+xcd_item\s*\(", txt)]
+    assert defs == ["work_split.h"], defs
+
+
 def test_no_function_local_static_state():
     """SURVEY §8(b) / include/lgm_render.h: no mutable state in the library besides the thread-local error and
     diagnostics scope -- no function-local statics (a per-process "attribute already set" flag would skip a second
