@@ -6,7 +6,10 @@ one HIP runtime per process and letting device pointers and streams flow between
 
 The library holds no mutable global state besides its thread-local error string: diagnostics (the kernel profiler,
 the render work counters) travel with each call as an `lgm_diag` (include/lgm_common.h). The harness-side switch
-for them is `diagnostics(...)` here, whose value every wrapper passes as the call's `diag` (None = NULL).
+for them is `diagnostics(...)` here, whose value `call` passes as every call's `diag` (None = NULL).
+
+SIGNATURES and the constants below are hand copies of include/*.h (the package loads without the headers);
+tests/test_abi.py compares them with the headers entry by entry.
 """
 from __future__ import annotations
 
@@ -155,12 +158,52 @@ def check(rc: int, what: str):
         raise NativeError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
 
 
+# The calling convention of every wrapper in this package (DESIGN §1 "Calling the C ABI from Python"):
+#   nat.call("lgm_x", dev, scalars..., nat.ptr(t)..., nat.ptr(ws), ws_bytes)     a compute entry point
+#   ws, ws_bytes = nat.workspace("lgm_x_workspace_size", dev, dims...)            its workspace
+#   nat.dtype_code(t.dtype, "x", DTYPES)                                          its dtype arguments
+# Entry points that do not end in (stream, diag) -- the *_workspace_size functions, the render inspection copies, the
+# profiler -- are called on lib() directly, their return code through check().
+
 def ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    """A tensor's address as a plain int (None: NULL), which ctypes takes for a void * parameter as it is."""
+    return None if t is None else t.data_ptr()
 
 
-def stream_of(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def stream_of(device) -> int:
+    """The handle of `device`'s current stream, as an int (torch's raw getter where there is one: a
+    torch.cuda.Stream object costs microseconds)."""
+    index = getattr(device, "index", None)
+    if _get_raw_stream is not None and isinstance(index, int):  # (a device without an index, or its name: the Stream)
+        return _get_raw_stream(index)
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def call(name: str, device, *args):
+    """The compute entry point `name`(*args, stream, diag) on `device`'s current stream; a non-zero return raises
+    NativeError with `name` and the library's error text. `args` go to ctypes as they are: pointers as ptr(t)."""
+    rc = getattr(lib(), name)(*args, stream_of(device), diag())
+    if rc:
+        check(rc, name)
+
+
+def workspace(size_fn: str, device, *dims, min_bytes: int = 1):
+    """(uint8 tensor, workspace_bytes) for what the library's `size_fn`(*dims) asks: max(workspace_bytes, min_bytes)
+    bytes, so that the pointer is never NULL; with min_bytes=0 a zero size allocates nothing and the tensor is None."""
+    ws_bytes = getattr(lib(), size_fn)(*dims)
+    n = max(ws_bytes, min_bytes)
+    return (torch.empty(n, dtype=torch.uint8, device=device) if n else None), ws_bytes
+
+
+def dtype_code(dtype, who: str, accepted=DTYPE_CODES) -> int:
+    """The C ABI's code of `dtype` (DTYPE_CODES), which must be one of `accepted`."""
+    if dtype not in accepted:
+        names = "/".join(str(d).replace("torch.", "") for d in accepted)
+        raise NativeError(f"{who} supports {names}, got {dtype}")
+    return DTYPE_CODES[dtype]
 
 
 def require_device_tensor(t: torch.Tensor, name: str):

@@ -19,13 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._native import dtype_code, ptr  # (the kernels here take every dtype of nat.DTYPE_CODES)
 from .linear import linear as _linear16
-
-
-def _dtype_code(t: torch.Tensor) -> int:
-    if t.dtype not in nat.DTYPE_CODES:
-        raise nat.NativeError(f"attention supports float32/bfloat16/float16, got {t.dtype}")
-    return nat.DTYPE_CODES[t.dtype]
 
 
 class _PackedAttention(torch.autograd.Function):
@@ -38,15 +33,13 @@ class _PackedAttention(torch.autograd.Function):
         B, L, three, H, D = qkv.shape
         if three != 3:
             raise nat.NativeError(f"qkv must be [B, L, 3, H, D], got {tuple(qkv.shape)}")
-        dt = _dtype_code(qkv)
+        dt = dtype_code(qkv.dtype, "attention")
         o = torch.empty((B, L, H, D), device=qkv.device, dtype=qkv.dtype)
         lse = torch.empty((B, H, L), device=qkv.device, dtype=torch.float32)
         if B * L * H > 0:
-            base, es = qkv.data_ptr(), qkv.element_size()
-            L_ = nat.lib()
-            nat.check(L_.lgm_attn_forward(dt, B, L, H, D, float(scale), base, base + H * D * es,
-                                          base + 2 * H * D * es, 3 * H * D, nat.ptr(o), nat.ptr(lse),
-                                          nat.stream_of(qkv.device), nat.diag()), "lgm_attn_forward")
+            base, hd = ptr(qkv), H * D * qkv.element_size()
+            nat.call("lgm_attn_forward", qkv.device, dt, B, L, H, D, float(scale), base, base + hd, base + 2 * hd,
+                     3 * H * D, ptr(o), ptr(lse))
         ctx.save_for_backward(qkv, o, lse)
         ctx.scale = float(scale)
         return o
@@ -58,16 +51,12 @@ class _PackedAttention(torch.autograd.Function):
         d_o = d_o.to(qkv.dtype).contiguous()
         d_qkv = torch.empty_like(qkv)
         if B * L * H > 0:
-            dt = _dtype_code(qkv)
-            L_ = nat.lib()
-            ws_bytes = L_.lgm_attn_workspace_size(dt, B, L, H, D)
-            ws = torch.empty(max(ws_bytes, 1), device=qkv.device, dtype=torch.uint8)
-            base, dbase, es = qkv.data_ptr(), d_qkv.data_ptr(), qkv.element_size()
-            hd = H * D * es
-            nat.check(L_.lgm_attn_backward(dt, B, L, H, D, ctx.scale, base, base + hd, base + 2 * hd, 3 * H * D,
-                                           nat.ptr(o), nat.ptr(lse), nat.ptr(d_o), dbase, dbase + hd,
-                                           dbase + 2 * hd, 3 * H * D, nat.ptr(ws), ws_bytes,
-                                           nat.stream_of(qkv.device), nat.diag()), "lgm_attn_backward")
+            dt = dtype_code(qkv.dtype, "attention")
+            ws, ws_bytes = nat.workspace("lgm_attn_workspace_size", qkv.device, dt, B, L, H, D)
+            base, dbase, hd = ptr(qkv), ptr(d_qkv), H * D * qkv.element_size()
+            nat.call("lgm_attn_backward", qkv.device, dt, B, L, H, D, ctx.scale, base, base + hd, base + 2 * hd,
+                     3 * H * D, ptr(o), ptr(lse), ptr(d_o), dbase, dbase + hd, dbase + 2 * hd, 3 * H * D, ptr(ws),
+                     ws_bytes)
         return d_qkv, None
 
 
@@ -166,13 +155,10 @@ class _NormTokens(torch.autograd.Function):
         rstd = torch.empty((BF, groups), device=x.device, dtype=torch.float32)
         w = None if weight is None else weight.detach().float().contiguous()
         b = None if bias is None else bias.detach().float().contiguous()
-        L_ = nat.lib()
-        ws_bytes = L_.lgm_mva_workspace_size(B, F, C, HW, groups)
-        ws = torch.empty(max(ws_bytes, 1), device=x.device, dtype=torch.uint8)
-        nat.check(L_.lgm_mva_norm_tokens(_dtype_code(x), _dtype_code(tok), B, F, C, HW, groups, float(eps), nat.ptr(x),
-                                         nat.ptr(w), nat.ptr(b), nat.ptr(tok), nat.ptr(mean), nat.ptr(rstd),
-                                         nat.ptr(ws), ws_bytes, nat.stream_of(x.device), nat.diag()),
-                  "lgm_mva_norm_tokens")
+        ws, ws_bytes = nat.workspace("lgm_mva_workspace_size", x.device, B, F, C, HW, groups)
+        nat.call("lgm_mva_norm_tokens", x.device, dtype_code(x.dtype, "attention"), dtype_code(tok_dtype, "attention"),
+                 B, F, C, HW, groups, float(eps), ptr(x), ptr(w), ptr(b), ptr(tok), ptr(mean), ptr(rstd), ptr(ws),
+                 ws_bytes)
         ctx.save_for_backward(x, weight, mean, rstd)
         ctx.shape = (B, F, C, H, W, groups)
         ctx.set_materialize_grads(False)
@@ -193,15 +179,11 @@ class _NormTokens(torch.autograd.Function):
         dx = torch.empty_like(x) if need_x else None
         dw = torch.empty(C, device=x.device, dtype=torch.float32) if need_w else None
         db = torch.empty(C, device=x.device, dtype=torch.float32) if need_b else None
-        L_ = nat.lib()
-        ws_bytes = L_.lgm_mva_backward_workspace_size(B, F, C, H * W, groups)
-        ws = torch.empty(max(ws_bytes, 1), device=x.device, dtype=torch.uint8)
+        ws, ws_bytes = nat.workspace("lgm_mva_backward_workspace_size", x.device, B, F, C, H * W, groups)
         gamma = None if weight is None else weight.detach().float().contiguous()
-        nat.check(L_.lgm_mva_norm_tokens_backward(_dtype_code(x), _dtype_code(d_tok), B, F, C, H * W, groups,
-                                                  nat.ptr(x), nat.ptr(gamma), nat.ptr(mean), nat.ptr(rstd),
-                                                  nat.ptr(d_tok), nat.ptr(d_res), nat.ptr(dx), nat.ptr(dw),
-                                                  nat.ptr(db), nat.ptr(ws), ws_bytes, nat.stream_of(x.device),
-                                                  nat.diag()), "lgm_mva_norm_tokens_backward")
+        nat.call("lgm_mva_norm_tokens_backward", x.device, dtype_code(x.dtype, "attention"),
+                 dtype_code(d_tok.dtype, "attention"), B, F, C, H * W, groups, ptr(x), ptr(gamma), ptr(mean), ptr(rstd),
+                 ptr(d_tok), ptr(d_res), ptr(dx), ptr(dw), ptr(db), ptr(ws), ws_bytes)
         dw = None if dw is None else dw.to(weight.dtype)
         db = None if db is None else db.to(weight.dtype)
         return dx, dw, db, None, None, None, None
@@ -219,9 +201,9 @@ class _TokensOut(torch.autograd.Function):
         out_dtype = y.dtype if res is None else torch.promote_types(y.dtype, res.dtype)
         out = torch.empty((B * F, C, H, W), device=y.device, dtype=out_dtype)
         r = None if res is None else res.contiguous()
-        nat.check(nat.lib().lgm_mva_tokens_out(_dtype_code(y), 0 if r is None else _dtype_code(r), _dtype_code(out),
-                                               B, F, C, H * W, nat.ptr(y), nat.ptr(r), float(skip), nat.ptr(out),
-                                               nat.stream_of(y.device), nat.diag()), "lgm_mva_tokens_out")
+        nat.call("lgm_mva_tokens_out", y.device, dtype_code(y.dtype, "attention"),
+                 0 if r is None else dtype_code(r.dtype, "attention"), dtype_code(out_dtype, "attention"), B, F, C, H * W,
+                 ptr(y), ptr(r), float(skip), ptr(out))
         ctx.meta = (B, F, C, H, W, float(skip), y.dtype, None if res is None else res.dtype)
         return out
 
@@ -232,11 +214,9 @@ class _TokensOut(torch.autograd.Function):
         d_y = torch.empty((B, F * H * W, C), device=d_out.device, dtype=ydt)
         want_res = rdt is not None and ctx.needs_input_grad[1]
         d_res = torch.empty((B * F, C, H, W), device=d_out.device, dtype=rdt) if want_res else None
-        nat.check(nat.lib().lgm_mva_tokens_out_backward(_dtype_code(d_out), _dtype_code(d_y),
-                                                        _dtype_code(d_res) if want_res else 0, B, F, C, H * W,
-                                                        nat.ptr(d_out), skip if rdt is not None else 1.0,
-                                                        nat.ptr(d_y), nat.ptr(d_res), nat.stream_of(d_out.device),
-                                                        nat.diag()), "lgm_mva_tokens_out_backward")
+        nat.call("lgm_mva_tokens_out_backward", d_out.device, dtype_code(d_out.dtype, "attention"),
+                 dtype_code(ydt, "attention"), dtype_code(rdt, "attention") if want_res else 0, B, F, C, H * W,
+                 ptr(d_out), skip if rdt is not None else 1.0, ptr(d_y), ptr(d_res))
         return d_y, d_res, None, None, None, None
 
 

@@ -19,8 +19,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
+from ._native import ptr
 
-_CODES = (torch.bfloat16, torch.float16)  # the operand dtypes the kernels take (codes: nat.DTYPE_CODES)
+DTYPES = (torch.bfloat16, torch.float16)  # the operand dtypes the kernels take
 _GRID_MAX = 2 ** 31 - 1
 
 
@@ -31,12 +32,9 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, ksize: int, want_db: bool):
     Cin = x.shape[1]
     dw = torch.empty((Cout, Cin, ksize, ksize), device=dy.device, dtype=torch.float32)
     db = torch.empty((Cout,), device=dy.device, dtype=torch.float32) if want_db else None
-    L = nat.lib()
-    ws_bytes = L.lgm_conv_wgrad_workspace_size(N, Cin, Cout, H, W, ksize, int(want_db))
-    ws = torch.empty(max(ws_bytes, 1), device=dy.device, dtype=torch.uint8)
-    nat.check(L.lgm_conv_wgrad(nat.DTYPE_CODES[dy.dtype], N, Cin, Cout, H, W, ksize, nat.ptr(dy), nat.ptr(x), nat.ptr(dw),
-                               nat.ptr(db), nat.ptr(ws), ws_bytes, nat.stream_of(dy.device), nat.diag()),
-              "lgm_conv_wgrad")
+    ws, ws_bytes = nat.workspace("lgm_conv_wgrad_workspace_size", dy.device, N, Cin, Cout, H, W, ksize, int(want_db))
+    nat.call("lgm_conv_wgrad", dy.device, nat.DTYPE_CODES[dy.dtype], N, Cin, Cout, H, W, ksize, ptr(dy), ptr(x), ptr(dw),
+             ptr(db), ptr(ws), ws_bytes)
     return dw, db
 
 
@@ -52,12 +50,9 @@ def conv_forward(x16: torch.Tensor, w: torch.Tensor, bias, ksize: int) -> torch.
     Cout = w.shape[0]
     dt = x16.dtype
     y = torch.empty((N, Cout, H, W), device=x16.device, dtype=dt)
-    L = nat.lib()
-    ws_bytes = L.lgm_conv_forward_workspace_size(N, Cin, Cout, H, W, ksize)
-    ws = torch.empty(max(ws_bytes, 1), device=x16.device, dtype=torch.uint8)
-    nat.check(L.lgm_conv_forward(nat.DTYPE_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, nat.ptr(x16), nat.ptr(w),
-                                 nat.ptr(bias), 0 if bias is None else _w_code(bias, dt), nat.ptr(y), nat.ptr(ws),
-                                 ws_bytes, nat.stream_of(x16.device), nat.diag()), "lgm_conv_forward")
+    ws, ws_bytes = nat.workspace("lgm_conv_forward_workspace_size", x16.device, N, Cin, Cout, H, W, ksize)
+    nat.call("lgm_conv_forward", x16.device, nat.DTYPE_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, ptr(x16),
+             ptr(w), ptr(bias), 0 if bias is None else _w_code(bias, dt), ptr(y), ptr(ws), ws_bytes)
     return y
 
 
@@ -68,12 +63,9 @@ def conv_dgrad(dy16: torch.Tensor, w: torch.Tensor, ksize: int) -> torch.Tensor:
     Cin = w.shape[1]
     dt = dy16.dtype
     dx = torch.empty((N, Cin, H, W), device=dy16.device, dtype=dt)
-    L = nat.lib()
-    ws_bytes = L.lgm_conv_dgrad_workspace_size(N, Cin, Cout, H, W, ksize)
-    ws = torch.empty(max(ws_bytes, 1), device=dy16.device, dtype=torch.uint8)
-    nat.check(L.lgm_conv_dgrad(nat.DTYPE_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, nat.ptr(dy16), nat.ptr(w),
-                               nat.ptr(dx), nat.ptr(ws), ws_bytes, nat.stream_of(dy16.device), nat.diag()),
-              "lgm_conv_dgrad")
+    ws, ws_bytes = nat.workspace("lgm_conv_dgrad_workspace_size", dy16.device, N, Cin, Cout, H, W, ksize)
+    nat.call("lgm_conv_dgrad", dy16.device, nat.DTYPE_CODES[dt], _w_code(w, dt), N, Cin, Cout, H, W, ksize, ptr(dy16),
+             ptr(w), ptr(dx), ptr(ws), ws_bytes)
     return dx
 
 
@@ -181,12 +173,12 @@ def _takes_kind(x: torch.Tensor, conv: nn.Conv2d):
         dt = torch.get_autocast_dtype("cuda")
         if not x.is_floating_point():
             return None
-    elif x.dtype in _CODES and w.dtype == x.dtype:
+    elif x.dtype in DTYPES and w.dtype == x.dtype:
         dt = x.dtype
     else:
         return None
     k = conv.kernel_size[0]
-    if dt not in _CODES or conv.kernel_size not in ((1, 1), (3, 3)) or conv.stride != (1, 1) or \
+    if dt not in DTYPES or conv.kernel_size not in ((1, 1), (3, 3)) or conv.stride != (1, 1) or \
             conv.dilation != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros" or conv.transposed:
         return None
     pad = (k - 1) // 2

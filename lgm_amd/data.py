@@ -22,7 +22,6 @@ them ready-made (how the tests replay the reference's draws).
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -32,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as nat
+from ._native import ptr
 from .cameras import projection_matrix
 from .options import Options
 
@@ -118,11 +118,9 @@ def data_cameras(c2w: torch.Tensor, Vi: int, jitter: Optional[torch.Tensor], jit
     cam_view, cam_view_proj = torch.empty(B, V, 4, 4, device=dev), torch.empty(B, V, 4, 4, device=dev)
     cam_pos, colmap = torch.empty(B, V, 3, device=dev), torch.empty(B, Vi, 4, 4, device=dev)
     with torch.cuda.device(dev):
-        rc = nat.lib().lgm_data_cameras(B, V, Vi, nat.ptr(c2w), nat.ptr(jitter), float(jitter_strength),
-                                        float(cam_radius), float(fovy), float(znear), float(zfar), nat.ptr(pose_in),
-                                        nat.ptr(cam_view), nat.ptr(cam_view_proj), nat.ptr(cam_pos), nat.ptr(colmap),
-                                        nat.stream_of(dev), nat.diag())
-    nat.check(rc, "lgm_data_cameras")
+        nat.call("lgm_data_cameras", dev, B, V, Vi, ptr(c2w), ptr(jitter), float(jitter_strength), float(cam_radius),
+                 float(fovy), float(znear), float(zfar), ptr(pose_in), ptr(cam_view), ptr(cam_view_proj), ptr(cam_pos),
+                 ptr(colmap))
     return pose_in, cam_view, cam_view_proj, cam_pos, colmap
 
 
@@ -142,22 +140,19 @@ def data_views(src: torch.Tensor, pose_in: Optional[torch.Tensor], knots: Option
     inp = torch.empty(B, Vi, 9, h, h, device=dev) if want_input else None
     img = torch.empty(B, V, 3, So, So, device=dev) if want_output else None
     msk = torch.empty(B, V, 1, So, So, device=dev) if want_output else None
-    nk = None
     if knots is not None:
         knots = knots.to(dev, torch.int32).contiguous()
         nknots = nknots.to("cpu", torch.int32).contiguous()
         assert knots.shape == (B, Vi, 2, MAX_KNOTS) and nknots.shape == (B, Vi), (knots.shape, nknots.shape)
-        nk = ctypes.c_void_p(nknots.data_ptr())
     if want_input:
         pose_in = _f32c(pose_in.to(dev))
         assert pose_in.shape == (B, Vi, 4, 4), pose_in.shape
     flags = (SWAP_RB if swap_rb else 0) | (0 if normalize else NO_NORMALIZE)
     with torch.cuda.device(dev):
-        rc = nat.lib().lgm_data_views(nat.DATA_U8 if src.dtype == torch.uint8 else 0, flags, B, V, Vi, Hs, Ws, h, So,
-                                      nat.ptr(src), nat.ptr(pose_in) if want_input else None, nat.ptr(knots), nk,
-                                      float(fovy), nat.ptr(inp), nat.ptr(img), nat.ptr(msk), nat.stream_of(dev),
-                                      nat.diag())
-    nat.check(rc, "lgm_data_views")
+        # (nknots is a host array: the one pointer here that is not a device address)
+        nat.call("lgm_data_views", dev, nat.DATA_U8 if src.dtype == torch.uint8 else 0, flags, B, V, Vi, Hs, Ws, h, So,
+                 ptr(src), ptr(pose_in) if want_input else None, ptr(knots), ptr(nknots) if knots is not None else None,
+                 float(fovy), ptr(inp), ptr(img), ptr(msk))
     return inp, img, msk
 
 

@@ -14,7 +14,8 @@ import os
 import numpy as np
 import torch
 
-from . import _native
+from . import _native as nat
+from ._native import ptr
 from .ply import read_ply, write_ply
 
 # Slot-mode (sync-free, worst-case B*V*T*N pair slots) workspace when it fits; otherwise the pairs are counted
@@ -44,52 +45,49 @@ def _tiles(H: int, W: int) -> int:
     return ((W + 15) // 16) * ((H + 15) // 16)
 
 
+def _count_pairs(g, cam_view, cam_view_proj, tanx, tany, scale_modifier, H, W):
+    """lgm_render_count_pairs -> device int64 [2]: the (binned, reference) pair counts over all B x V views."""
+    B, N, V = g.shape[0], g.shape[1], cam_view.shape[1]
+    ws, ws_bytes = nat.workspace("lgm_render_workspace_size", g.device, B, V, N, H, W, 1, min_bytes=0)
+    k = torch.zeros(2, dtype=torch.int64, device=g.device)
+    nat.call("lgm_render_count_pairs", g.device, B, V, N, H, W, ptr(g), ptr(cam_view), ptr(cam_view_proj), tanx, tany,
+             scale_modifier, ptr(ws), ws_bytes, ptr(k))
+    return k
+
+
 class _RasterizeBatched(torch.autograd.Function):
     """Autograd Function over all B x V renders (replaces B*V applications of the EXT _RasterizeGaussians)."""
 
     @staticmethod
     def forward(ctx, g, cam_view, cam_view_proj, bg, tanx, tany, scale_modifier, H, W, options, gt_img=None,
                 gt_mask=None):
-        L = _native.lib()
+        L = nat.lib()
         B, N = g.shape[0], g.shape[1]
         V = cam_view.shape[1]
         dev = g.device
-        stream = _native.stream_of(dev)
         cap = 0
         ws_bytes = L.lgm_render_workspace_size_opts(B, V, N, H, W, 0, options)
         if not _slot_fits(ws_bytes, dev):
             # exact pair count (the reference syncs once per view for this; we sync once per batch)
-            small = L.lgm_render_workspace_size(B, V, N, H, W, 1)
-            ws = torch.empty(small, dtype=torch.uint8, device=dev)
-            k = torch.zeros(2, dtype=torch.int64, device=dev)
-            _native.check(L.lgm_render_count_pairs(B, V, N, H, W, _native.ptr(g), _native.ptr(cam_view),
-                                                   _native.ptr(cam_view_proj), tanx, tany, scale_modifier,
-                                                   _native.ptr(ws), small, _native.ptr(k), stream, _native.diag()),
-                          "lgm_render_count_pairs")
+            k = _count_pairs(g, cam_view, cam_view_proj, tanx, tany, scale_modifier, H, W)
             # pairs actually binned (upstream's full count with LGM_RENDER_NO_CULL)
-            cap = max(int(k[1 if options & _native.RENDER_NO_CULL else 0].item()), 1)
+            cap = max(int(k[1 if options & nat.RENDER_NO_CULL else 0].item()), 1)
             ws_bytes = L.lgm_render_workspace_size_opts(B, V, N, H, W, cap, options)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)  # (sized above: not one nat.workspace question)
         image = torch.empty(B, V, 3, H, W, dtype=torch.float32, device=dev)
         depth = torch.empty(B, V, 1, H, W, dtype=torch.float32, device=dev)
         alpha = torch.empty(B, V, 1, H, W, dtype=torch.float32, device=dev)
         if gt_img is None:
             loss4 = torch.empty(0, dtype=torch.float32, device=dev)
-            _native.check(L.lgm_render_forward(B, V, N, H, W, _native.ptr(g), _native.ptr(cam_view),
-                                               _native.ptr(cam_view_proj), _native.ptr(bg), tanx, tany, scale_modifier,
-                                               _native.ptr(image), _native.ptr(depth), _native.ptr(alpha), None,
-                                               _native.ptr(ws), ws_bytes, cap, None, options, stream,
-                                               _native.diag()),
-                          "lgm_render_forward")
+            nat.call("lgm_render_forward", dev, B, V, N, H, W, ptr(g), ptr(cam_view), ptr(cam_view_proj), ptr(bg), tanx,
+                     tany, scale_modifier, ptr(image), ptr(depth), ptr(alpha), None, ptr(ws), ws_bytes, cap, None,
+                     options)
         else:
             # (loss_mse, mse_image, mse_alpha, psnr) of core/models.py:145-148,167, computed by the kernels
             loss4 = torch.empty(4, dtype=torch.float32, device=dev)
-            _native.check(L.lgm_render_forward_loss(B, V, N, H, W, _native.ptr(g), _native.ptr(cam_view),
-                                                    _native.ptr(cam_view_proj), _native.ptr(bg), tanx, tany,
-                                                    scale_modifier, _native.ptr(image), _native.ptr(depth),
-                                                    _native.ptr(alpha), _native.ptr(gt_img), _native.ptr(gt_mask),
-                                                    _native.ptr(loss4), _native.ptr(ws), ws_bytes, cap, options,
-                                                    stream, _native.diag()), "lgm_render_forward_loss")
+            nat.call("lgm_render_forward_loss", dev, B, V, N, H, W, ptr(g), ptr(cam_view), ptr(cam_view_proj), ptr(bg),
+                     tanx, tany, scale_modifier, ptr(image), ptr(depth), ptr(alpha), ptr(gt_img), ptr(gt_mask),
+                     ptr(loss4), ptr(ws), ws_bytes, cap, options)
         # the workspace is saved like an input: autograd frees it after a (non-retain_graph) backward, so a training
         # loop that keeps the previous step's outputs alive does not hold two workspaces
         ctx.save_for_backward(g, cam_view, cam_view_proj, bg, ws, gt_img, gt_mask, loss4)
@@ -109,10 +107,8 @@ class _RasterizeBatched(torch.autograd.Function):
         d_depth = None if d_depth is None else d_depth.float().contiguous()
         d_alpha = None if d_alpha is None else d_alpha.float().contiguous()
         d_g = torch.empty_like(g)
-        L = _native.lib()
-        bwd_options = options | (_native.RENDER_BACKWARD_AGAIN if ctx.backwards else 0)
+        bwd_options = options | (nat.RENDER_BACKWARD_AGAIN if ctx.backwards else 0)
         ctx.backwards += 1
-        stream = _native.stream_of(g.device)
         if gt_img is not None and d_loss4 is not None:
             if d_depth is not None:
                 raise NotImplementedError("a depth gradient together with the fused loss (LGM's loss has no depth)")
@@ -122,18 +118,13 @@ class _RasterizeBatched(torch.autograd.Function):
             # reference computes it under no_grad): an exact fit (mse_image == 0) must not turn 0 / 0 into NaN
             d_psnr = torch.where(d4[3] != 0, d4[3] * (10.0 / math.log(10.0)) / loss4[1], torch.zeros_like(d4[3]))
             s2 = torch.stack([d4[0] + d4[1] - d_psnr, d4[0] + d4[2]]).contiguous()
-            _native.check(L.lgm_render_backward_loss(B, V, N, H, W, _native.ptr(g), _native.ptr(cam_view),
-                                                     _native.ptr(cam_view_proj), _native.ptr(bg), tanx, tany,
-                                                     scale_modifier, _native.ptr(d_image), _native.ptr(d_alpha),
-                                                     _native.ptr(gt_img), _native.ptr(gt_mask), _native.ptr(s2),
-                                                     _native.ptr(d_g), _native.ptr(ws), ctx.ws_bytes, ctx.cap,
-                                                     bwd_options, stream, _native.diag()), "lgm_render_backward_loss")
+            nat.call("lgm_render_backward_loss", g.device, B, V, N, H, W, ptr(g), ptr(cam_view), ptr(cam_view_proj),
+                     ptr(bg), tanx, tany, scale_modifier, ptr(d_image), ptr(d_alpha), ptr(gt_img), ptr(gt_mask), ptr(s2),
+                     ptr(d_g), ptr(ws), ctx.ws_bytes, ctx.cap, bwd_options)
         else:
-            _native.check(L.lgm_render_backward(B, V, N, H, W, _native.ptr(g), _native.ptr(cam_view),
-                                                _native.ptr(cam_view_proj), _native.ptr(bg), tanx, tany, scale_modifier,
-                                                _native.ptr(d_image), _native.ptr(d_depth), _native.ptr(d_alpha),
-                                                _native.ptr(d_g), None, _native.ptr(ws), ctx.ws_bytes, ctx.cap,
-                                                bwd_options, stream, _native.diag()), "lgm_render_backward")
+            nat.call("lgm_render_backward", g.device, B, V, N, H, W, ptr(g), ptr(cam_view), ptr(cam_view_proj), ptr(bg),
+                     tanx, tany, scale_modifier, ptr(d_image), ptr(d_depth), ptr(d_alpha), ptr(d_g), None, ptr(ws),
+                     ctx.ws_bytes, ctx.cap, bwd_options)
         return d_g, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -161,7 +152,7 @@ def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, sc
         mi, ma = torch.nn.functional.mse_loss(out[0], gt_c), torch.nn.functional.mse_loss(out[2], gt_masks)
         return out + (torch.stack([mi + ma, mi, ma, -10 * torch.log10(mi)]),)
     for t, n in ((gaussians, "gaussians"), (cam_view, "cam_view"), (cam_view_proj, "cam_view_proj")):
-        _native.require_device_tensor(t, n)
+        nat.require_device_tensor(t, n)
     g = gaussians.float().contiguous()
     dev = g.device
     cv = cam_view.to(dev, torch.float32).contiguous()
@@ -178,9 +169,9 @@ def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, sc
         gtm = gt_masks.to(dev, torch.float32).contiguous().detach()
         if tuple(gti.shape) != (B, V, 3, H, W) or tuple(gtm.shape) != (B, V, 1, H, W):
             raise ValueError("gt_images / gt_masks must be [B,V,3,H,W] / [B,V,1,H,W]")
-    options = (_native.RENDER_CLAMP_IMAGE if clamp else 0) | (_native.RENDER_NO_CULL if no_cull else 0)
+    options = (nat.RENDER_CLAMP_IMAGE if clamp else 0) | (nat.RENDER_NO_CULL if no_cull else 0)
     if deterministic_enabled() if deterministic is None else deterministic:
-        options |= _native.RENDER_DETERMINISTIC
+        options |= nat.RENDER_DETERMINISTIC
     out = _RasterizeBatched.apply(g, cv, cvp, bgt, float(tanfovx), float(tanfovy), float(scale_modifier),
                                   int(H), int(W), options, gti, gtm)
     return out if gti is not None else out[:3]
@@ -189,20 +180,10 @@ def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, sc
 def count_pairs(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, scale_modifier=1.0):
     """(binned, reference) (Gaussian, tile) pair counts over all B x V views (one host sync): `binned` after the
     exact opacity-aware tile culling, `reference` = upstream's num_rendered summed over views (SURVEY §8(d)'s K)."""
-    L = _native.lib()
     g = gaussians.float().contiguous()
-    B, N, V = g.shape[0], g.shape[1], cam_view.shape[1]
-    dev = g.device
-    small = L.lgm_render_workspace_size(B, V, N, H, W, 1)
-    ws = torch.empty(small, dtype=torch.uint8, device=dev)
-    k = torch.zeros(2, dtype=torch.int64, device=dev)
-    cv = cam_view.to(dev, torch.float32).contiguous()
-    cvp = cam_view_proj.to(dev, torch.float32).contiguous()
-    _native.check(L.lgm_render_count_pairs(B, V, N, H, W, _native.ptr(g), _native.ptr(cv), _native.ptr(cvp),
-                                           float(tanfovx), float(tanfovy), float(scale_modifier), _native.ptr(ws),
-                                           small, _native.ptr(k), _native.stream_of(dev), _native.diag()),
-                  "lgm_render_count_pairs")
-    kk = k.tolist()
+    cv = cam_view.to(g.device, torch.float32).contiguous()
+    cvp = cam_view_proj.to(g.device, torch.float32).contiguous()
+    kk = _count_pairs(g, cv, cvp, float(tanfovx), float(tanfovy), float(scale_modifier), H, W).tolist()
     return int(kk[0]), int(kk[1])
 
 
@@ -214,36 +195,32 @@ def forward_state(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, sc
       n_contrib, final_T [B,V,H,W]; with lists=True, ids[b][v] = the view's tile lists concatenated (tile-major,
       each in compositing order); with records=True, the compositing records P, Q [B,V,N,4] and rects [B,V,N,2]
       (uint32) of lgm_render_records. no_cull=True bins upstream's full 3-sigma rects (LGM_RENDER_NO_CULL)."""
-    options = _native.RENDER_NO_CULL if no_cull else 0
-    L = _native.lib()
+    options = nat.RENDER_NO_CULL if no_cull else 0
+    L = nat.lib()
     g = gaussians.float().contiguous()
     dev = g.device
     B, N, V = g.shape[0], g.shape[1], cam_view.shape[1]
     cv = cam_view.to(dev, torch.float32).contiguous()
     cvp = cam_view_proj.to(dev, torch.float32).contiguous()
-    stream = _native.stream_of(dev)
-    ws_bytes = L.lgm_render_workspace_size(B, V, N, H, W, 0)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    stream = nat.stream_of(dev)  # (the inspection copies below take a stream and no diag: plain lib() calls)
+    ws, ws_bytes = nat.workspace("lgm_render_workspace_size", dev, B, V, N, H, W, 0, min_bytes=0)
     bg = torch.zeros(3, device=dev)
     image = torch.empty(B, V, 3, H, W, device=dev)
     depth = torch.empty(B, V, 1, H, W, device=dev)
     alpha = torch.empty(B, V, 1, H, W, device=dev)
     radii = torch.empty(B, V, N, dtype=torch.int32, device=dev)
     stats = torch.zeros(2, dtype=torch.int64, device=dev)
-    _native.check(L.lgm_render_forward(B, V, N, H, W, _native.ptr(g), _native.ptr(cv), _native.ptr(cvp),
-                                       _native.ptr(bg), float(tanfovx), float(tanfovy), float(scale_modifier),
-                                       _native.ptr(image), _native.ptr(depth), _native.ptr(alpha), _native.ptr(radii),
-                                       _native.ptr(ws), ws_bytes, 0, _native.ptr(stats), options, stream,
-                                       _native.diag()),
-                  "lgm_render_forward")
+    nat.call("lgm_render_forward", dev, B, V, N, H, W, ptr(g), ptr(cv), ptr(cvp), ptr(bg), float(tanfovx),
+             float(tanfovy), float(scale_modifier), ptr(image), ptr(depth), ptr(alpha), ptr(radii), ptr(ws), ws_bytes, 0,
+             ptr(stats), options)
     T = _tiles(H, W)
     counts = torch.empty(B * V * T, dtype=torch.int32, device=dev)
-    _native.check(L.lgm_render_tile_lists(B, V, N, H, W, _native.ptr(ws), ws_bytes, 0, _native.ptr(counts), None,
-                                          None, stream), "lgm_render_tile_lists")
+    nat.check(L.lgm_render_tile_lists(B, V, N, H, W, ptr(ws), ws_bytes, 0, ptr(counts), None, None, stream),
+              "lgm_render_tile_lists")
     n_contrib = torch.empty(B, V, H, W, dtype=torch.int32, device=dev)
     final_T = torch.empty(B, V, H, W, dtype=torch.float32, device=dev)
-    _native.check(L.lgm_render_pixel_state(B, V, N, H, W, _native.ptr(ws), ws_bytes, 0, _native.ptr(n_contrib),
-                                           _native.ptr(final_T), stream), "lgm_render_pixel_state")
+    nat.check(L.lgm_render_pixel_state(B, V, N, H, W, ptr(ws), ws_bytes, 0, ptr(n_contrib), ptr(final_T), stream),
+              "lgm_render_pixel_state")
     out = {"radii": radii.cpu().numpy(), "tile_counts": counts.view(B, V, T).cpu().numpy(),
            "n_contrib": n_contrib.cpu().numpy(), "final_T": final_T.cpu().numpy()}
     k = stats.tolist()
@@ -253,8 +230,8 @@ def forward_state(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, sc
         offsets = (torch.cumsum(c64, 0) - c64).contiguous()
         total = int(c64.sum().item())
         ids = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-        _native.check(L.lgm_render_tile_lists(B, V, N, H, W, _native.ptr(ws), ws_bytes, 0, _native.ptr(counts),
-                                              _native.ptr(offsets), _native.ptr(ids), stream), "lgm_render_tile_lists")
+        nat.check(L.lgm_render_tile_lists(B, V, N, H, W, ptr(ws), ws_bytes, 0, ptr(counts), ptr(offsets), ptr(ids),
+                                          stream), "lgm_render_tile_lists")
         flat = ids[:total].cpu().numpy()
         per_view = c64.view(B * V, T).sum(1).tolist()
         bounds = np.concatenate([[0], np.cumsum(per_view)])
@@ -263,8 +240,8 @@ def forward_state(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, sc
         P = torch.empty(B, V, N, 4, device=dev)
         Q = torch.empty(B, V, N, 4, device=dev)
         rects = torch.empty(B, V, N, 2, dtype=torch.int32, device=dev)
-        _native.check(L.lgm_render_records(B, V, N, H, W, _native.ptr(ws), ws_bytes, 0, _native.ptr(P), _native.ptr(Q),
-                                           _native.ptr(rects), stream), "lgm_render_records")
+        nat.check(L.lgm_render_records(B, V, N, H, W, ptr(ws), ws_bytes, 0, ptr(P), ptr(Q), ptr(rects), stream),
+                  "lgm_render_records")
         out["P"], out["Q"] = P.cpu().numpy(), Q.cpu().numpy()
         out["rects"] = rects.cpu().numpy().view(np.uint32)
     return out

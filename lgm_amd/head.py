@@ -20,16 +20,16 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._native import ptr
 
-_DT = (torch.float32, torch.bfloat16)  # the input dtypes the kernels take (codes: nat.DTYPE_CODES)
+DTYPES = (torch.float32, torch.bfloat16)  # the input dtypes the kernels take
 
 
 class _Head(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, B, V):
         nat.require_device_tensor(x, "x")
-        if x.dtype not in _DT:
-            raise nat.NativeError(f"gaussian_head supports float32 / bfloat16 inputs, got {x.dtype}")
+        code = nat.dtype_code(x.dtype, "gaussian_head", DTYPES)
         BV, C, h, w = x.shape
         if C != 14 or BV != B * V:
             raise ValueError(f"x must be [B*V, 14, h, w] with B*V = {B * V}, got {tuple(x.shape)}")
@@ -38,12 +38,9 @@ class _Head(torch.autograd.Function):
         b = None if bias is None else bias.detach().float().contiguous()
         out = torch.empty(B, V * h * w, 14, device=x.device, dtype=torch.float32)
         rot_norm = torch.empty(B, 4, device=x.device, dtype=torch.float32)
-        L = nat.lib()
-        ws_bytes = L.lgm_gaussian_head_workspace_size(B, V, h, w)
-        ws = torch.empty(max(ws_bytes, 1), device=x.device, dtype=torch.uint8)
-        nat.check(L.lgm_gaussian_head_forward(nat.DTYPE_CODES[x.dtype], B, V, h, w, nat.ptr(x), nat.ptr(W), nat.ptr(b),
-                                              nat.ptr(out), nat.ptr(rot_norm), nat.ptr(ws), ws_bytes,
-                                              nat.stream_of(x.device), nat.diag()), "lgm_gaussian_head_forward")
+        ws, ws_bytes = nat.workspace("lgm_gaussian_head_workspace_size", x.device, B, V, h, w)
+        nat.call("lgm_gaussian_head_forward", x.device, code, B, V, h, w, ptr(x), ptr(W), ptr(b), ptr(out),
+                 ptr(rot_norm), ptr(ws), ws_bytes)
         ctx.save_for_backward(x, W, b if b is not None else W.new_empty(0), rot_norm)
         ctx.dims = (B, V, h, w, bias is not None, weight.shape, weight.dtype, None if bias is None else bias.dtype)
         return out
@@ -52,18 +49,13 @@ class _Head(torch.autograd.Function):
     def backward(ctx, d_out):
         x, W, b, rot_norm = ctx.saved_tensors
         B, V, h, w, has_bias, wshape, wdtype, bdtype = ctx.dims
-        L = nat.lib()
         d_out = d_out.float().contiguous()
         dx = torch.empty_like(x)
         dW = torch.empty(14, 14, device=x.device, dtype=torch.float32)
         db = torch.empty(14, device=x.device, dtype=torch.float32) if has_bias else None
-        ws_bytes = L.lgm_gaussian_head_workspace_size(B, V, h, w)
-        ws = torch.empty(max(ws_bytes, 1), device=x.device, dtype=torch.uint8)
-        nat.check(L.lgm_gaussian_head_backward(nat.DTYPE_CODES[x.dtype], B, V, h, w, nat.ptr(x), nat.ptr(W),
-                                               nat.ptr(b) if has_bias else None, nat.ptr(rot_norm), nat.ptr(d_out),
-                                               nat.ptr(dx),
-                                               nat.ptr(dW), nat.ptr(db), nat.ptr(ws), ws_bytes,
-                                               nat.stream_of(x.device), nat.diag()), "lgm_gaussian_head_backward")
+        ws, ws_bytes = nat.workspace("lgm_gaussian_head_workspace_size", x.device, B, V, h, w)
+        nat.call("lgm_gaussian_head_backward", x.device, nat.DTYPE_CODES[x.dtype], B, V, h, w, ptr(x), ptr(W),
+                 ptr(b) if has_bias else None, ptr(rot_norm), ptr(d_out), ptr(dx), ptr(dW), ptr(db), ptr(ws), ws_bytes)
         return dx, dW.reshape(wshape).to(wdtype), None if db is None else db.to(bdtype), None, None
 
 

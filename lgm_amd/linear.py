@@ -13,8 +13,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as nat
+from ._native import ptr
 
-_CODES = (torch.bfloat16, torch.float16)  # the operand dtypes the kernel takes (codes: nat.DTYPE_CODES)
+DTYPES = (torch.bfloat16, torch.float16)  # the operand dtypes the kernel takes
 
 
 class _Linear16(torch.autograd.Function):
@@ -45,12 +46,9 @@ class _Linear16(torch.autograd.Function):
             K = x2.shape[0]
             dw = torch.empty((M, N), device=g.device, dtype=torch.float32)
             db = torch.empty((M,), device=g.device, dtype=torch.float32) if want_b else None
-            L = nat.lib()
-            ws_bytes = L.lgm_linear_wgrad_workspace_size(K, M, N, int(want_b))
-            ws = torch.empty(max(ws_bytes, 1), device=g.device, dtype=torch.uint8)
-            nat.check(L.lgm_linear_wgrad(nat.DTYPE_CODES[dt], K, M, N, nat.ptr(g2), M, nat.ptr(x2), N, nat.ptr(dw), nat.ptr(db),
-                                         nat.ptr(ws), ws_bytes, nat.stream_of(g.device), nat.diag()),
-                      "lgm_linear_wgrad")
+            ws, ws_bytes = nat.workspace("lgm_linear_wgrad_workspace_size", g.device, K, M, N, int(want_b))
+            nat.call("lgm_linear_wgrad", g.device, nat.DTYPE_CODES[dt], K, M, N, ptr(g2), M, ptr(x2), N, ptr(dw),
+                     ptr(db), ptr(ws), ws_bytes)
             dw = dw.to(wdt) if want_w else None
             db = None if db is None else db.to(bdt)
         return gx, dw, db, None
@@ -58,7 +56,7 @@ class _Linear16(torch.autograd.Function):
 
 def _supported(x: torch.Tensor, weight: torch.Tensor, dt) -> bool:
     M, N = weight.shape
-    return dt in _CODES and x.is_cuda and M % 8 == 0 and N % 8 == 0
+    return dt in DTYPES and x.is_cuda and M % 8 == 0 and N % 8 == 0
 
 
 def linear(x: torch.Tensor, lin: torch.nn.Linear) -> torch.Tensor:
@@ -70,7 +68,7 @@ def linear(x: torch.Tensor, lin: torch.nn.Linear) -> torch.Tensor:
         return lin(x)
     if x.is_cuda and torch.is_autocast_enabled("cuda"):
         dt = torch.get_autocast_dtype("cuda")
-    elif x.dtype in _CODES and lin.weight.dtype == x.dtype:
+    elif x.dtype in DTYPES and lin.weight.dtype == x.dtype:
         dt = x.dtype
     else:
         return lin(x)

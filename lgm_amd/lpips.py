@@ -29,9 +29,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
-from ._native import DTYPE_CODES as _DTYPES
+from ._native import ptr
 from .attention import _autocast_dtype
-from .unet import _raw_stream
+
+# Deprecated and unused in this package: the name under which the GPU tests of earlier revisions import the table.
+# New code and new tests say nat.DTYPE_CODES.
+_DTYPES = nat.DTYPE_CODES
 
 # torchvision's vgg16().features: (index, in, out) of the convolutions; a ReLU follows each; max-pools at POOLS
 CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
@@ -122,7 +125,7 @@ def _torch_distance(f0, f1, w, eps):
 
 
 class _LpipsDist(torch.autograd.Function):
-    """lgm_lpips_dist_forward / _backward. Pointers go to the C ABI as plain integers (None = NULL)."""
+    """lgm_lpips_dist_forward / _backward (the dtypes are _dist_takes' to check)."""
 
     @staticmethod
     def forward(ctx, f0, f1, w, eps: float):
@@ -133,16 +136,11 @@ class _LpipsDist(torch.autograd.Function):
         need0, need1 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         out = torch.empty(N, device=dev, dtype=torch.float32)
         norms = torch.empty((2, N, H, W), device=dev, dtype=torch.float32) if need0 or need1 else None
-        L_ = nat.lib()
-        ws_bytes = L_.lgm_lpips_dist_workspace_size(N, C, H, W)
-        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-        code = _DTYPES[f0.dtype]
-        np_ = None if norms is None else norms.data_ptr()
-        rc = L_.lgm_lpips_dist_forward(code, _DTYPES[f1.dtype], N, C, H, W, eps, f0.data_ptr(), f1.data_ptr(),
-                                       w.data_ptr(), out.data_ptr(), np_, None if np_ is None else np_ + 4 * N * H * W,
-                                       ws.data_ptr(), ws_bytes, _raw_stream(dev), nat.diag())
-        if rc:
-            nat.check(rc, "lgm_lpips_dist_forward")
+        ws, ws_bytes = nat.workspace("lgm_lpips_dist_workspace_size", dev, N, C, H, W, min_bytes=0)
+        np_ = ptr(norms)
+        nat.call("lgm_lpips_dist_forward", dev, nat.DTYPE_CODES[f0.dtype], nat.DTYPE_CODES[f1.dtype], N, C, H, W, eps,
+                 ptr(f0), ptr(f1), ptr(w), ptr(out), np_, None if np_ is None else np_ + 4 * N * H * W, ptr(ws),
+                 ws_bytes)
         if norms is not None:
             ctx.save_for_backward(f0, f1, w, norms)
             ctx.eps = eps
@@ -156,15 +154,10 @@ class _LpipsDist(torch.autograd.Function):
         g = g.float().contiguous()
         df0 = torch.empty_like(f0) if need0 else None
         df1 = torch.empty_like(f1) if need1 else None
-        code = _DTYPES[f0.dtype]
-        np_ = norms.data_ptr()
-        rc = nat.lib().lgm_lpips_dist_backward(code, code, N, C, H, W, ctx.eps, f0.data_ptr(), f1.data_ptr(),
-                                               w.data_ptr(), np_, np_ + 4 * N * H * W, g.data_ptr(),
-                                               None if df0 is None else df0.data_ptr(),
-                                               None if df1 is None else df1.data_ptr(), _raw_stream(f0.device),
-                                               nat.diag())
-        if rc:
-            nat.check(rc, "lgm_lpips_dist_backward")
+        code = nat.DTYPE_CODES[f0.dtype]
+        np_ = ptr(norms)
+        nat.call("lgm_lpips_dist_backward", f0.device, code, code, N, C, H, W, ctx.eps, ptr(f0), ptr(f1), ptr(w), np_,
+                 np_ + 4 * N * H * W, ptr(g), ptr(df0), ptr(df1))
         return df0, df1, None, None
 
 
@@ -178,11 +171,8 @@ class _LpipsPrep(torch.autograd.Function):
         gt, mask, bg = gt.float().contiguous(), mask.float().contiguous(), bg.float().contiguous()
         xp = torch.empty((M, 3, R, R), device=pred.device, dtype=dtype)
         xg = torch.empty_like(xp)
-        rc = nat.lib().lgm_lpips_prep_forward(_DTYPES[dtype], M, S, R, pred.data_ptr(), gt.data_ptr(), mask.data_ptr(),
-                                              bg.data_ptr(), xp.data_ptr(), xg.data_ptr(), _raw_stream(pred.device),
-                                              nat.diag())
-        if rc:
-            nat.check(rc, "lgm_lpips_prep_forward")
+        nat.call("lgm_lpips_prep_forward", pred.device, nat.DTYPE_CODES[dtype], M, S, R, ptr(pred), ptr(gt),
+                 ptr(mask), ptr(bg), ptr(xp), ptr(xg))
         ctx.meta = (M, S, R, dtype)
         ctx.mark_non_differentiable(xg)
         return xp, xg
@@ -192,10 +182,7 @@ class _LpipsPrep(torch.autograd.Function):
         M, S, R, dtype = ctx.meta
         d_xp = d_xp.to(dtype).contiguous()
         d_pred = torch.empty((M, 3, S, S), device=d_xp.device, dtype=torch.float32)
-        rc = nat.lib().lgm_lpips_prep_backward(_DTYPES[dtype], M, S, R, d_xp.data_ptr(), d_pred.data_ptr(),
-                                               _raw_stream(d_xp.device), nat.diag())
-        if rc:
-            nat.check(rc, "lgm_lpips_prep_backward")
+        nat.call("lgm_lpips_prep_backward", d_xp.device, nat.DTYPE_CODES[dtype], M, S, R, ptr(d_xp), ptr(d_pred))
         return d_pred, None, None, None, None, None
 
 
@@ -203,7 +190,7 @@ def _dist_takes(f0, f1, w) -> bool:
     """What lgm_lpips_dist_* accepts (include/lgm_lpips.h); everything else is torch's."""
     if not (f0.is_cuda and f1.device == f0.device and w.device == f0.device) or f0.dim() != 4 or f0.shape != f1.shape:
         return False
-    if f0.dtype not in _DTYPES or f1.dtype != f0.dtype or w.dtype not in _DTYPES or f0.numel() == 0:
+    if f0.dtype not in nat.DTYPE_CODES or f1.dtype != f0.dtype or w.dtype not in nat.DTYPE_CODES or f0.numel() == 0:
         return False
     if w.requires_grad and torch.is_grad_enabled():  # trainable heads: the kernels return no gradient for them
         return False
@@ -282,7 +269,7 @@ class LPIPS(nn.Module):
         M, C, S, S2 = pred.shape
         if C != 3 or S != S2 or M == 0 or gt.shape != pred.shape or mask.shape != (M, 1, S, S) or bg.numel() != 3:
             return False
-        if any(t.device != pred.device or t.dtype not in _DTYPES for t in (pred, gt, mask, bg)):
+        if any(t.device != pred.device or t.dtype not in nat.DTYPE_CODES for t in (pred, gt, mask, bg)):
             return False
         if torch.is_grad_enabled() and (gt.requires_grad or mask.requires_grad or bg.requires_grad):
             return False  # the input kernel differentiates with respect to pred only
@@ -298,7 +285,8 @@ class LPIPS(nn.Module):
         mask = gt_masks.reshape(-1, 1, S, S)
         if self._prep_takes(pred, gt, mask, bg_color):
             ac = _autocast_dtype("cuda")
-            x_pred, x_gt = _LpipsPrep.apply(pred, gt, mask, bg_color, self.size, ac if ac in _DTYPES else torch.float32)
+            x_pred, x_gt = _LpipsPrep.apply(pred, gt, mask, bg_color, self.size,
+                                            ac if ac in nat.DTYPE_CODES else torch.float32)
             return self._distance(x_gt, x_pred)
         gt = gt * mask + bg_color.view(1, 3, 1, 1) * (1 - mask)
         R = (self.size, self.size)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._native import ptr
 from .ply import write_mesh_ply
 
 CUTOFF = 1e-4  # include/lgm_mesh.h LGM_MESH_CUTOFF
@@ -90,24 +91,22 @@ def _check_gaussians(g: torch.Tensor) -> torch.Tensor:
 
 def _density_native(g, G, lo, h, scale_modifier, cutoff, sigma, rgb):
     dev = g.device
-    L = nat.lib()
     N = g.shape[0]
     lo_c, h_c = _c3(lo), _c3(h)
     with torch.cuda.device(dev):
-        ws0 = torch.empty(max(L.lgm_mesh_density_workspace_size(N, *G, 0), 1), dtype=torch.uint8, device=dev)
+        # (these entry points are told the allocated size: ws.numel(), at least 1)
+        ws0, _ = nat.workspace("lgm_mesh_density_workspace_size", dev, N, *G, 0)
         npairs = torch.zeros(1, dtype=torch.int64, device=dev)
-        rc = L.lgm_mesh_density_count(nat.ptr(g) if N else None, N, float(scale_modifier), *G, lo_c, h_c, float(cutoff),
-                                      nat.ptr(ws0), ws0.numel(), nat.ptr(npairs), nat.stream_of(dev), nat.diag())
-        nat.check(rc, "lgm_mesh_density_count")
+        nat.call("lgm_mesh_density_count", dev, ptr(g) if N else None, N, float(scale_modifier), *G, lo_c, h_c,
+                 float(cutoff), ptr(ws0), ws0.numel(), ptr(npairs))
         cap = int(npairs.item())  # the lists' length is data dependent: the one host sync of the density pass
         if cap >= 2 ** 31:
             raise nat.NativeError(f"lgm_mesh_density: {cap} (Gaussian, brick) pairs, the lists are indexed with 31 bits; "
                                   "raise the cutoff or lower the resolution")
         del ws0
-        ws = torch.empty(max(L.lgm_mesh_density_workspace_size(N, *G, cap), 1), dtype=torch.uint8, device=dev)
-        rc = L.lgm_mesh_density(nat.ptr(g) if N else None, N, float(scale_modifier), *G, lo_c, h_c, float(cutoff), cap,
-                                nat.ptr(sigma), nat.ptr(rgb), nat.ptr(ws), ws.numel(), nat.stream_of(dev), nat.diag())
-        nat.check(rc, "lgm_mesh_density")
+        ws, _ = nat.workspace("lgm_mesh_density_workspace_size", dev, N, *G, cap)
+        nat.call("lgm_mesh_density", dev, ptr(g) if N else None, N, float(scale_modifier), *G, lo_c, h_c, float(cutoff),
+                 cap, ptr(sigma), ptr(rgb), ptr(ws), ws.numel())
 
 
 def _density_torch(g, G, lo, h, scale_modifier, cutoff, sigma, rgb):
@@ -182,21 +181,16 @@ def density_grid(gaussians: torch.Tensor, resolution: Union[int, Sequence[int]] 
 # ------------------------------------------------------------------------------------------------------- extraction
 def _extract_native(sigma, rgb, iso, G, lo, h) -> Mesh:
     dev = sigma.device
-    L = nat.lib()
     with torch.cuda.device(dev):
-        ws = torch.empty(max(L.lgm_mesh_extract_workspace_size(*G), 1), dtype=torch.uint8, device=dev)
+        ws, _ = nat.workspace("lgm_mesh_extract_workspace_size", dev, *G)  # (passed as ws.numel(), as above)
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
-        rc = L.lgm_mesh_count(nat.ptr(sigma), *G, float(iso), nat.ptr(ws), ws.numel(), nat.ptr(counts),
-                              nat.stream_of(dev), nat.diag())
-        nat.check(rc, "lgm_mesh_count")
+        nat.call("lgm_mesh_count", dev, ptr(sigma), *G, float(iso), ptr(ws), ws.numel(), ptr(counts))
         nv, nf = counts.tolist()  # the one host sync: the outputs' sizes
         vertices = torch.empty(nv, 3, dtype=torch.float32, device=dev)
         colors = torch.empty(nv, 3, dtype=torch.float32, device=dev) if rgb is not None else None
         faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-        rc = L.lgm_mesh_emit(nat.ptr(sigma), nat.ptr(rgb), *G, _c3(lo), _c3(h), float(iso), nat.ptr(ws), ws.numel(), nv,
-                             nf, nat.ptr(vertices), nat.ptr(colors), nat.ptr(faces), nv, nf, nat.stream_of(dev),
-                             nat.diag())
-        nat.check(rc, "lgm_mesh_emit")
+        nat.call("lgm_mesh_emit", dev, ptr(sigma), ptr(rgb), *G, _c3(lo), _c3(h), float(iso), ptr(ws), ws.numel(), nv,
+                 nf, ptr(vertices), ptr(colors), ptr(faces), nv, nf)
     return Mesh(vertices, faces, colors)
 
 

@@ -12,7 +12,6 @@ GPU tensors run the kernels; CPU tensors take torch's own functional forms.
 """
 from __future__ import annotations
 
-import ctypes
 import weakref
 from typing import Iterable, Optional, Union
 
@@ -20,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._native import ptr
 
 CHUNK = nat.OPTIM_CHUNK
 _ROW = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel", "<i4"), ("chunk0", "<i4")])
@@ -75,18 +75,14 @@ class _Lists:
         """k_optim_sqnorm + k_optim_reduce -> device float32 [2]: (norm, coef)."""
         out = torch.empty(2, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = nat.lib().lgm_optim_grad_norm(nat.ptr(self.table), len(self.rows), nat.ptr(self.chunk_tensor),
-                                               self.nchunks, float(max_norm), nat.ptr(self.partials),
-                                               self.partials.numel() * 8, nat.ptr(out), nat.stream_of(dev), nat.diag())
-        nat.check(rc, "lgm_optim_grad_norm")
+            nat.call("lgm_optim_grad_norm", dev, ptr(self.table), len(self.rows), ptr(self.chunk_tensor), self.nchunks,
+                     float(max_norm), ptr(self.partials), self.partials.numel() * 8, ptr(out))
         return out
 
     def scale(self, out: torch.Tensor, dev: torch.device):
         with torch.cuda.device(dev):
-            rc = nat.lib().lgm_optim_scale(nat.ptr(self.table), len(self.rows), nat.ptr(self.chunk_tensor),
-                                           self.nchunks, ctypes.c_void_p(out.data_ptr() + 4), nat.stream_of(dev),
-                                           nat.diag())
-        nat.check(rc, "lgm_optim_scale")
+            nat.call("lgm_optim_scale", dev, ptr(self.table), len(self.rows), ptr(self.chunk_tensor), self.nchunks,
+                     out.data_ptr() + 4)
 
     def adamw(self, first: int, last: int, out: Optional[torch.Tensor], dev: torch.device, lr, beta1, beta2, eps, wd,
               step):
@@ -95,12 +91,10 @@ class _Lists:
         end = int(self.chunk0[last]) if last < len(self.rows) else self.nchunks
         if end == begin:
             return
-        coef = None if out is None else ctypes.c_void_p(out.data_ptr() + 4)
+        coef = None if out is None else out.data_ptr() + 4
         with torch.cuda.device(dev):
-            rc = nat.lib().lgm_optim_adamw(nat.ptr(self.table), len(self.rows), nat.ptr(self.chunk_tensor), begin,
-                                           end - begin, coef, float(lr), float(beta1), float(beta2), float(eps),
-                                           float(wd), float(step), nat.stream_of(dev), nat.diag())
-        nat.check(rc, "lgm_optim_adamw")
+            nat.call("lgm_optim_adamw", dev, ptr(self.table), len(self.rows), ptr(self.chunk_tensor), begin, end - begin,
+                     coef, float(lr), float(beta1), float(beta2), float(eps), float(wd), float(step))
 
 
 def _dense(t: torch.Tensor) -> bool:

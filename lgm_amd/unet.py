@@ -23,10 +23,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as nat
-from ._native import DTYPE_CODES as _DTYPES
+from ._native import ptr
 from .attention import MemEffAttention, MVAttention, _autocast_dtype
 from .conv import conv2d, conv2d_native
 from .cpu import attention_cpu
+
+# Deprecated and unused in this package: the name under which the GPU tests of earlier revisions import the table.
+# New code and new tests say nat.DTYPE_CODES.
+_DTYPES = nat.DTYPE_CODES
 
 _RESAMPLE = {None: 0, "default": 0, "up": 1, "down": 2}  # include/lgm_norm.h LGM_GN_RESAMPLE_*
 _GRID_MAX = 2 ** 31 - 1
@@ -67,15 +71,8 @@ def _f32(p):
     return None if p is None else p.detach().float().contiguous()
 
 
-def _raw_stream(dev) -> int:
-    """The current stream's handle (torch's raw getter: the Stream object of nat.stream_of costs microseconds, and
-    this wrapper runs twice per GroupNorm site)."""
-    get = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-    return get(dev.index) if get is not None and dev.index is not None else nat.stream_of(dev).value
-
-
 class _GnSilu(torch.autograd.Function):
-    """lgm_gn_silu_forward / lgm_gn_silu_backward. Pointers go to the C ABI as plain integers (None = NULL)."""
+    """lgm_gn_silu_forward / lgm_gn_silu_backward (the dtypes are _kernel_takes' to check)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, groups: int, eps: float, rs: int, y_dtype):
@@ -85,16 +82,11 @@ class _GnSilu(torch.autograd.Function):
         y = torch.empty((N, C, oh, ow), device=x.device, dtype=y_dtype)
         stats = torch.empty((2, N, groups), device=x.device, dtype=torch.float32)  # mean, rstd
         w, b = _f32(weight), _f32(bias)
-        L_ = nat.lib()
-        ws_bytes = L_.lgm_gn_silu_workspace_size(N, C, H, W, groups)  # (0 where one launch does it)
-        ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8) if ws_bytes else None
-        sp = stats.data_ptr()
-        rc = L_.lgm_gn_silu_forward(_DTYPES[x.dtype], _DTYPES[y_dtype], N, C, H, W, groups, eps, rs, x.data_ptr(),
-                                    None if w is None else w.data_ptr(), None if b is None else b.data_ptr(),
-                                    y.data_ptr(), sp, sp + 4 * N * groups, None if ws is None else ws.data_ptr(),
-                                    ws_bytes, _raw_stream(x.device), nat.diag())
-        if rc:
-            nat.check(rc, "lgm_gn_silu_forward")
+        # (0 bytes where one launch does it: then nothing is allocated and the workspace is NULL)
+        ws, ws_bytes = nat.workspace("lgm_gn_silu_workspace_size", x.device, N, C, H, W, groups, min_bytes=0)
+        sp = ptr(stats)
+        nat.call("lgm_gn_silu_forward", x.device, nat.DTYPE_CODES[x.dtype], nat.DTYPE_CODES[y_dtype], N, C, H, W,
+                 groups, eps, rs, ptr(x), ptr(w), ptr(b), ptr(y), sp, sp + 4 * N * groups, ptr(ws), ws_bytes)
         ctx.save_for_backward(x, w, b, stats)
         ctx.meta = (groups, rs, y_dtype, None if weight is None else weight.dtype, None if bias is None else bias.dtype)
         return y
@@ -111,23 +103,18 @@ class _GnSilu(torch.autograd.Function):
         d_y = d_y.to(y_dtype).contiguous()
         dx = torch.empty_like(x) if need_x else None
         dwb = torch.empty((2, C), device=x.device, dtype=torch.float32) if need_w or need_b else None  # dgamma, dbeta
-        L_ = nat.lib()
-        ws_bytes = L_.lgm_gn_silu_backward_workspace_size(N, C, H, W, groups)
-        ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-        sp = stats.data_ptr()
-        rc = L_.lgm_gn_silu_backward(_DTYPES[x.dtype], _DTYPES[y_dtype], N, C, H, W, groups, rs, x.data_ptr(),
-                                     None if w is None else w.data_ptr(), None if b is None else b.data_ptr(), sp,
-                                     sp + 4 * N * groups, d_y.data_ptr(), None if dx is None else dx.data_ptr(),
-                                     dwb.data_ptr() if need_w else None, dwb.data_ptr() + 4 * C if need_b else None,
-                                     ws.data_ptr(), ws_bytes, _raw_stream(x.device), nat.diag())
-        if rc:
-            nat.check(rc, "lgm_gn_silu_backward")
+        ws, ws_bytes = nat.workspace("lgm_gn_silu_backward_workspace_size", x.device, N, C, H, W, groups, min_bytes=0)
+        sp = ptr(stats)
+        nat.call("lgm_gn_silu_backward", x.device, nat.DTYPE_CODES[x.dtype], nat.DTYPE_CODES[y_dtype], N, C, H, W,
+                 groups, rs, ptr(x), ptr(w), ptr(b), sp, sp + 4 * N * groups, ptr(d_y), ptr(dx),
+                 ptr(dwb) if need_w else None, ptr(dwb) + 4 * C if need_b else None, ptr(ws), ws_bytes)
         return dx, (dwb[0].to(wdt) if need_w else None), (dwb[1].to(bdt) if need_b else None), None, None, None, None
 
 
 def _kernel_takes(x: torch.Tensor, norm: nn.GroupNorm, rs: int, y_dtype) -> bool:
     """What lgm_gn_silu_* accepts (include/lgm_norm.h); everything else is torch's."""
-    if not x.is_cuda or x.dim() != 4 or x.dtype not in _DTYPES or y_dtype not in _DTYPES or x.numel() == 0:
+    if not x.is_cuda or x.dim() != 4 or x.numel() == 0 or x.dtype not in nat.DTYPE_CODES or \
+            y_dtype not in nat.DTYPE_CODES:
         return False
     if x.dtype != torch.float32 and y_dtype != x.dtype:
         return False
@@ -135,7 +122,7 @@ def _kernel_takes(x: torch.Tensor, norm: nn.GroupNorm, rs: int, y_dtype) -> bool
     if C != norm.num_channels or (rs == 2 and (H % 2 or W % 2)):
         return False
     for p in (norm.weight, norm.bias):
-        if p is not None and (p.device != x.device or p.dtype not in _DTYPES):
+        if p is not None and (p.device != x.device or p.dtype not in nat.DTYPE_CODES):
             return False
     # the launch grids (one workgroup per 1024 pixels of a plane, per 4096 elements of a group) and the element count
     return N * C * (-(-H * W // 1024)) <= _GRID_MAX and N * C * (-(-H * W // 4096) + 1) <= _GRID_MAX and \

@@ -29,6 +29,67 @@ def test_library_exports_all_declared_symbols():
     assert not [s for s in syms if s not in _native.SIGNATURES], [s for s in syms if s not in _native.SIGNATURES]
 
 
+def _headers():
+    """include/*.h as one text without comments."""
+    return "\n".join(re.sub(r"/\*.*?\*/|//[^\n]*", "", open(h).read(), flags=re.S)
+                     for h in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))))
+
+
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}
+
+
+def _ctype(decl: str, named: bool):
+    """The ctypes type of a C parameter (named) or return type: any pointer or array is c_void_p, void is None."""
+    if "*" in decl or "[" in decl:
+        return ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    base = " ".join(words[:-1] if named else words)
+    return None if base == "void" else _SCALARS[base]  # (a KeyError names a type this test has to learn)
+
+
+def header_prototypes():
+    """{name: (restype, [argtypes])} of every prototype in include/*.h."""
+    protos = {}
+    for ret, name, params in re.findall(r"^[ \t]*([A-Za-z_][\w \t\*]*?)\b(lgm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _headers(),
+                                        flags=re.M):
+        params = [p.strip() for p in params.split(",")]
+        args = [] if params == ["void"] else [_ctype(p, True) for p in params]
+        assert name not in protos, name
+        protos[name] = (_ctype(ret, False), args)
+    return protos
+
+
+def test_signatures_match_the_headers():
+    """Every entry of _native.SIGNATURES has the return and argument types of its prototype in include/*.h: an int
+    written where the header says long long or size_t would truncate silently. (c_char_p counts as a pointer.)"""
+    protos = header_prototypes()
+    assert set(protos) == declared_symbols()  # the parser saw every prototype
+    assert set(protos) == set(_native.SIGNATURES)
+
+    def norm(t):
+        return ctypes.c_void_p if t is ctypes.c_char_p else t
+
+    for name, (res, args) in sorted(protos.items()):
+        sres, sargs = _native.SIGNATURES[name]
+        assert norm(sres) is res, (name, "return", sres, res)
+        assert len(sargs) == len(args), (name, len(sargs), len(args))
+        for i, (s, a) in enumerate(zip(sargs, args)):
+            assert norm(s) is a, (name, "argument", i, s, a)
+
+
+def test_constants_match_the_headers():
+    """The constants _native.py copies from the headers have their #define's value."""
+    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(LGM_\w+)[ \t]+(-?\d+)[ \t]*$", _headers(),
+                                                flags=re.M)}
+    import torch
+    assert _native.DTYPE_CODES == {torch.float32: defines["LGM_ATTN_F32"], torch.bfloat16: defines["LGM_ATTN_BF16"],
+                                   torch.float16: defines["LGM_ATTN_F16"]}
+    for name in ("RENDER_NO_CULL", "RENDER_CLAMP_IMAGE", "RENDER_BACKWARD_AGAIN", "RENDER_DETERMINISTIC", "DATA_U8",
+                 "OPTIM_CHUNK"):
+        assert getattr(_native, name) == defines["LGM_" + name], name
+
+
 def test_workspace_and_errors():
     L = _native.lib()
     assert L.lgm_abi_version() == _native.ABI_VERSION

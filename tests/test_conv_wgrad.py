@@ -158,3 +158,20 @@ def test_db_null_and_profiler(cuda):
     prof.close()
     assert none is None and torch.equal(dw, dw2)
     assert ran["k_conv_wgrad"][0] == 1 and ran["k_conv_wgrad_reduce"][0] == 1 and len(ran) == 2, ran
+
+
+@pytest.mark.gpu
+def test_wrapper_raises_the_library_error(cuda):
+    """A call the library refuses, made through the wrapper (lgm_amd.conv.wgrad): NativeError with the entry point's
+    name and the library's own text; the error does not stick: the next, valid call is right (the bar of
+    test_conv_wgrad_vs_fp64)."""
+    from lgm_amd.conv import wgrad
+    dy, x = operands((3, 1, 8, 8, 4, 4), torch.bfloat16, cuda)
+    with pytest.raises(_native.NativeError) as err:
+        wgrad(dy, x, 5, True)
+    assert "lgm_conv_wgrad" in str(err.value) and "ksize must be 1 or 3" in str(err.value), str(err.value)
+    dw, db = wgrad(dy, x, 3, True)
+    rw, rb = truth(dy, x, 3)
+    ew, eb = rel(dw, rw), rel(db, rb)
+    print(f"wrapper after a refused call: dw rel L2 {ew:.2e}, db {eb:.2e}")
+    assert ew < 1e-5 and eb < 1e-5

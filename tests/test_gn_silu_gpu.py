@@ -12,7 +12,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from lgm_amd import _native as nat
-from lgm_amd.unet import _DTYPES, group_norm_silu
+from lgm_amd._native import DTYPE_CODES as _DTYPES
+from lgm_amd.unet import group_norm_silu
 
 pytestmark = pytest.mark.gpu
 

@@ -15,7 +15,8 @@ import torch.nn.functional as F
 
 from lgm_amd import LGM, LPIPS, Options
 from lgm_amd import _native as nat
-from lgm_amd.lpips import _DTYPES, _LpipsPrep, _torch_distance, lpips_distance
+from lgm_amd._native import DTYPE_CODES as _DTYPES
+from lgm_amd.lpips import _LpipsPrep, _torch_distance, lpips_distance
 from tests.golden.make_unet_golden import TINY
 from tests.test_lpips_cpu import lgm_data, random_lpips
 

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from lgm_amd import _native as nat
-from lgm_amd.unet import _DTYPES
+from lgm_amd._native import DTYPE_CODES as _DTYPES
 
 pytestmark = pytest.mark.gpu
 
