@@ -71,12 +71,53 @@
  * lgm_mesh_emit (k_mesh_emit) with the same sigma, grid, iso and workspace, the counts it read (nv, nf) and the
  * capacities of its buffers (cap_v vertices, cap_f faces). Nothing is ever written past a capacity.
  *
+ * ---- Sampling pass: lgm_mesh_sample_count, lgm_mesh_sample ---------------------------------------------------------
+ * The same field at M arbitrary points [M, 3] fp32: sigma [M], rgb [M, 3] (or NULL). For a point p, sigma(p) and rgb(p)
+ * are exactly the density pass's formulas with x = p: the same skip rules, the cut d2 <= rho2, both sums in ascending
+ * n in fp32, rgb = 0 where sigma = 0. The grid (G, lo, h) is only the acceleration structure and the domain: a point
+ * is sampled iff its three coordinates are finite and lo - h / 2 <= p <= lo + (G - 1/2) h on every axis, compared in
+ * fp64 (the half-cell margin: a mesh vertex rounded an ulp past the box is still sampled); every other point gets
+ * sigma = 0, rgb = 0. Two calls are bitwise equal; no float atomics.
+ * Kernels: k_mesh_sample_bin_count is k_mesh_bin_count with boxes over continuous intervals: in node units brick b of
+ * an axis owns [b BRICK, (b + 1) BRICK), the first brick from -1/2 and the last one to G - 1/2, and a Gaussian enters
+ * every brick its [c - ext, c + ext] meets (the density pass's boxes are node ranges: a cut that ends between two
+ * nodes of different bricks leaves the lower brick's list, where a point may still lie). k_mesh_scan_*, k_mesh_bin_fill
+ * as above. k_mesh_point_count (per point: the test above, its brick = floor of its fp64 node coordinate, clamped,
+ * over BRICK; one integer atomic; the outputs of a point that is not sampled), k_mesh_scan_*, k_mesh_point_fill (the
+ * bricks' point lists, any order: a point's sum is its own), k_mesh_sample (one workgroup per brick with points, 256
+ * points at a time, one per thread, against the brick's list ordered and staged as in k_mesh_density; the point and mu
+ * are both taken relative to the brick's first node in fp64 before rounding).
+ * lgm_mesh_sample_count is lgm_mesh_density_count for these lists (its workspace:
+ * lgm_mesh_sample_workspace_size(N, 0, Gx, Gy, Gz, 0)); lgm_mesh_sample takes a capacity >= that total and a workspace
+ * of lgm_mesh_sample_workspace_size(N, M, Gx, Gy, Gz, capacity) bytes. A capacity below the total: every sigma and rgb
+ * is NaN (the points that are not sampled too), nothing is written out of bounds. M == 0 and N == 0 are valid.
+ *
+ * ---- Atlas: lgm_mesh_atlas ------------------------------------------------------------------------------------------
+ * A per-quad texture atlas for a mesh of the extraction pass, whose faces 2q and 2q + 1 are the quad q: outward
+ * (q0, q1, q2), (q0, q2, q3) or flipped (q0, q2, q1), (q0, q3, q2) (read off the pair: the second face starts with the
+ * first one's q0; outward iff the first face's last index is the second one's middle index). Quad q gets the block of
+ * T x T texels (T >= 2) at column q mod cols, row q / cols of a texture of W = cols T by H = rows T texels
+ * (cols rows >= the number of quads, W and H at most LGM_MESH_ATLAS_MAX).
+ *   - points [nq][T][T][3], texel (i, j) at [q][j][i]: s = i / (T - 1), t = j / (T - 1) (i runs along q0 -> q1, j along
+ *     q1 -> q2); s >= t: (1 - s) v0 + (s - t) v1 + t v2, otherwise (1 - t) v0 + (t - s) v3 + s v2: the point of the
+ *     triangle that is drawn there. fp32, every operation rounded on its own, the three products summed left to right.
+ *     Texel (0, 0) is v0 and texel (T - 1, T - 1) is v2.
+ *   - uvs [nq][4][2]: entry k of quad q is the corner of q_k, (a, b) = (0, 0), (1, 0), (1, 1), (0, 1), at the pixel
+ *     centre x = x0 + 1/2 + a (T - 1), y = y0 + 1/2 + b (T - 1) with (x0, y0) = (T (q mod cols), T (q / cols)):
+ *     u = x / W, v = 1 - y / H (fp32, as above). Bilinear filtering inside a quad never leaves its block.
+ *   - face_uvs [nf][3] int32: for every face corner the index into uvs (4 q + k) of the vertex faces names there.
+ * A pair without that structure, or with an index outside [0, nv): its block's points are NaN (callers validate
+ * first: lgm_amd.mesh.bake_texture raises).
+ *
  * ---- Errors --------------------------------------------------------------------------------------------------------
  * rc < 0 (and lgm_last_error), with nothing launched, on: a required pointer that is null (g with N > 0, lo, h, ws,
  * npairs / counts, sigma, vertices with nv > 0, faces with nf > 0, colors with rgb given and nv > 0), N < 0 or
  * N >= 2^31, a grid axis < 3, Gx Gy Gz >= 2^31, a non-finite lo or scale_modifier, a non-finite or non-positive h, iso
  * or cutoff, a negative capacity or count, a capacity or count whose element count (3 per vertex or face, 1 per list
- * entry) is >= 2^31, a workspace shorter than the *_workspace_size, cap_v < nv or cap_f < nf.
+ * entry) is >= 2^31, a workspace shorter than the *_workspace_size, cap_v < nv or cap_f < nf. Sampling: the density
+ * pass's rules, and M < 0, 3 M >= 2^31, points or sigma null with M > 0. Atlas: nv or nf negative, nf odd, 3 nv, 3 nf
+ * or 3 nq T T >= 2^31, T < 2, cols or rows < 1, cols rows < nq, cols T or rows T > LGM_MESH_ATLAS_MAX, a null pointer
+ * with nq > 0.
  * All work is enqueued on `stream` (a hipStream_t, NULL = default stream); nothing synchronises. The library keeps
  * no state: what lgm_mesh_count leaves for lgm_mesh_emit lives in the caller's workspace.
  */
@@ -91,6 +132,7 @@ extern "C" {
 #define LGM_MESH_CUTOFF 1e-4f  /* default eps: a Gaussian's term is dropped where it falls below this */
 #define LGM_MESH_BRICK 8       /* nodes per brick edge: one workgroup per brick */
 #define LGM_MESH_SORT_CAP 4096 /* longest brick list sorted in LDS; longer ones walk all N boxes in order */
+#define LGM_MESH_ATLAS_MAX 16384 /* widest and tallest atlas texture, in texels */
 
 /* bytes of the density workspace for N Gaussians on the grid with room for `capacity` list entries (0: the count
  * call); 0 on invalid sizes */
@@ -103,6 +145,21 @@ int lgm_mesh_density_count(const float *g, long long N, float scale_modifier, in
 int lgm_mesh_density(const float *g, long long N, float scale_modifier, int Gx, int Gy, int Gz, const float *lo,
                      const float *h, float cutoff, long long capacity, float *sigma, float *rgb, void *ws,
                      size_t ws_bytes, void *stream, const lgm_diag *diag);
+
+/* bytes of the sampling workspace for N Gaussians and M points (the count call: M = 0, capacity = 0); 0 on invalid
+ * sizes */
+size_t lgm_mesh_sample_workspace_size(long long N, long long M, int Gx, int Gy, int Gz, long long capacity);
+
+int lgm_mesh_sample_count(const float *g, long long N, float scale_modifier, int Gx, int Gy, int Gz, const float *lo,
+                          const float *h, float cutoff, void *ws, size_t ws_bytes, long long *npairs, void *stream,
+                          const lgm_diag *diag);
+
+int lgm_mesh_sample(const float *g, long long N, float scale_modifier, int Gx, int Gy, int Gz, const float *lo,
+                    const float *h, float cutoff, long long capacity, const float *points, long long M, float *sigma,
+                    float *rgb, void *ws, size_t ws_bytes, void *stream, const lgm_diag *diag);
+
+int lgm_mesh_atlas(const float *vertices, long long nv, const int *faces, long long nf, int T, int cols, int rows,
+                   float *points, float *uvs, int *face_uvs, void *stream, const lgm_diag *diag);
 
 /* bytes of the extraction workspace (shared by lgm_mesh_count and lgm_mesh_emit); 0 on invalid sizes */
 size_t lgm_mesh_extract_workspace_size(int Gx, int Gy, int Gz);

@@ -13,10 +13,10 @@ from .lpips import LPIPS
 from .models import LGM
 from .data import (build_batch, get_rays, grid_distortion, orbit_camera_jitter, plucker_rays, sample_grid_knots)
 from .optim import AdamW, clip_grad_norm_
-from .mesh import Mesh, density_grid, extract_surface, gaussians_to_mesh
+from .mesh import Mesh, bake_texture, density_grid, extract_surface, gaussians_to_mesh, sample_field
 
 __all__ = ["Options", "preset", "GaussianRenderer", "rasterize", "group_norm_silu", "ResnetBlock", "DownBlock",
            "MidBlock", "UpBlock", "UNet", "LGM", "LPIPS", "build_batch", "get_rays", "plucker_rays",
            "sample_grid_knots", "grid_distortion", "orbit_camera_jitter", "AdamW", "clip_grad_norm_", "Mesh",
-           "density_grid", "extract_surface", "gaussians_to_mesh"]
+           "density_grid", "extract_surface", "gaussians_to_mesh", "sample_field", "bake_texture"]
 __version__ = "0.1.0"

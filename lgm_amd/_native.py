@@ -107,6 +107,12 @@ SIGNATURES = {
                                         _vp, _vp, _vp]),
     "lgm_mesh_density": (_c_int, [_vp, _c_ll, _c_float, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _c_ll, _vp, _vp, _vp,
                                   _c_size, _vp, _vp]),
+    "lgm_mesh_sample_workspace_size": (_c_size, [_c_ll, _c_ll, _c_int, _c_int, _c_int, _c_ll]),
+    "lgm_mesh_sample_count": (_c_int, [_vp, _c_ll, _c_float, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_size,
+                                       _vp, _vp, _vp]),
+    "lgm_mesh_sample": (_c_int, [_vp, _c_ll, _c_float, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _c_ll, _vp, _c_ll,
+                                 _vp, _vp, _vp, _c_size, _vp, _vp]),
+    "lgm_mesh_atlas": (_c_int, [_vp, _c_ll, _vp, _c_ll, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "lgm_mesh_extract_workspace_size": (_c_size, [_c_int, _c_int, _c_int]),
     "lgm_mesh_count": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, _vp, _c_size, _vp, _vp, _vp]),
     "lgm_mesh_emit": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_size, _c_ll, _c_ll, _vp, _vp,

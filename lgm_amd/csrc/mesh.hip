@@ -11,6 +11,11 @@
 //                      order in LDS (rank sort up to 256 entries, bitonic up to LGM_MESH_SORT_CAP; longer lists are not
 //                      read: the workgroup walks all N boxes in order instead), stages 64 records at a time through
 //                      LDS and accumulates sum w and sum w c in fp32 in that order
+//   k_mesh_sample_bin_count / k_mesh_point_count / k_mesh_point_fill / k_mesh_sample
+//                      the same field at arbitrary points: the Gaussians binned over continuous brick intervals, the
+//                      points binned into bricks, one workgroup per brick walking its points 256 at a time against
+//                      its list (the list ordering and record staging are the device functions k_mesh_density uses)
+//   k_mesh_atlas       per texel of a per-quad T x T atlas: its point on the drawn triangle; per quad: its uvs
 //   k_mesh_classify    per node: the active flag of the cell it is the lowest corner of, and its triangle count
 //   k_mesh_emit        per node: the vertex and colour of its cell and the triangles of its three grid edges
 //
@@ -50,9 +55,11 @@ __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.4028235
 // ---------------------------------------------------------------------------------------------------- binning
 // record: mu (3), A' = sqrt(log2(e) / 2) diag(s)^-1 R^T row-major (9), log2 o, rgb (3).  box: brick ranges
 // [x0, x1, y0, y1, z0, z1, -, -], inclusive; x0 > x1: touches nothing.
-__global__ __launch_bounds__(THREADS) void k_mesh_bin_count(const float *__restrict__ g, int N, float mod, Grid gr,
-                                                            float cutoff, float4 *__restrict__ rec,
-                                                            int4 *__restrict__ box, int *__restrict__ cnt) {
+// SAMPLE: the boxes of the sampling pass, over continuous intervals (brick b owns [b BR, (b + 1) BR) in node units, the
+// first one from -1/2 and the last one to G - 1/2), so that a point between two nodes finds every Gaussian that reaches it
+template <bool SAMPLE>
+__device__ __forceinline__ void bin_count(const float *__restrict__ g, int N, float mod, const Grid &gr, float cutoff,
+                                          float4 *__restrict__ rec, int4 *__restrict__ box, int *__restrict__ cnt) {
     const int n = blockIdx.x * THREADS + threadIdx.x;
     if (n >= N) return;
     float f[14];
@@ -91,8 +98,12 @@ __global__ __launch_bounds__(THREADS) void k_mesh_bin_count(const float *__restr
             const double e0 = R[a][0] * s[0], e1 = R[a][1] * s[1], e2 = R[a][2] * s[2];
             const double ext = rho * sqrt(e0 * e0 + e1 * e1 + e2 * e2) * (1.0 + 1e-6);
             const double c = (double)f[a] - (double)gr.lo[a], hh = gr.h[a], top = gr.G[a] - 1;
-            const double i0 = fmax((c - ext) / hh - 1e-3, 0.0), i1 = fmin((c + ext) / hh + 1e-3, top);
-            if (i0 <= i1 && ceil(i0) <= floor(i1)) {  // (false for NaN too)
+            const double edge = SAMPLE ? 0.5 : 0.0;
+            const double i0 = fmax((c - ext) / hh - 1e-3, -edge), i1 = fmin((c + ext) / hh + 1e-3, top + edge);
+            if (SAMPLE && i0 <= i1) {  // (false for NaN too)
+                b0[a] = (int)floor(fmax(i0, 0.0)) / BR;
+                b1[a] = (int)floor(fmax(i1, 0.0)) / BR;  // (i1 <= G - 1/2: at most the last brick)
+            } else if (!SAMPLE && i0 <= i1 && ceil(i0) <= floor(i1)) {
                 b0[a] = (int)ceil(i0) / BR;
                 b1[a] = (int)floor(i1) / BR;
             } else {
@@ -110,6 +121,18 @@ __global__ __launch_bounds__(THREADS) void k_mesh_bin_count(const float *__restr
     for (int bx = b0[0]; bx <= b1[0]; bx++)
         for (int by = b0[1]; by <= b1[1]; by++)
             for (int bz = b0[2]; bz <= b1[2]; bz++) atomicAdd(&cnt[(bx * gr.nb[1] + by) * gr.nb[2] + bz], 1);
+}
+
+__global__ __launch_bounds__(THREADS) void k_mesh_bin_count(const float *__restrict__ g, int N, float mod, Grid gr,
+                                                            float cutoff, float4 *__restrict__ rec,
+                                                            int4 *__restrict__ box, int *__restrict__ cnt) {
+    bin_count<false>(g, N, mod, gr, cutoff, rec, box, cnt);
+}
+
+__global__ __launch_bounds__(THREADS) void k_mesh_sample_bin_count(const float *__restrict__ g, int N, float mod, Grid gr,
+                                                                   float cutoff, float4 *__restrict__ rec,
+                                                                   int4 *__restrict__ box, int *__restrict__ cnt) {
+    bin_count<true>(g, N, mod, gr, cutoff, rec, box, cnt);
 }
 
 __global__ __launch_bounds__(THREADS) void k_mesh_bin_fill(int N, Grid gr, const int4 *__restrict__ box,
@@ -206,6 +229,93 @@ struct NodeAcc {
     float w, r, g, b;
 };
 
+// The three steps k_mesh_density and k_mesh_sample share. Every thread of the workgroup calls them (barriers inside).
+//
+// s_list[0 .. L) = src[0 .. L) in ascending order, L <= LGM_MESH_SORT_CAP. Returns without a barrier: for_each_record
+// begins with one.
+__device__ __forceinline__ void order_list(const int *__restrict__ src, int L, int *s_list) {
+    const int tid = threadIdx.x;
+    if (L <= RANK_CAP) {
+        // rank sort: the indices of a list are distinct, so the number of smaller ones is the place
+        int *tmp = s_list + RANK_CAP;
+        const int v = tid < L ? src[tid] : 0x7fffffff;
+        tmp[tid] = v;
+        __syncthreads();
+        if (tid < L) {
+            int rank = 0;
+            for (int i = 0; i < L; i++) rank += tmp[i] < v;
+            s_list[rank] = v;
+        }
+    } else {
+        int P = RANK_CAP * 2;
+        while (P < L) P <<= 1;
+        for (int i = tid; i < P; i += THREADS) s_list[i] = i < L ? src[i] : 0x7fffffff;
+        __syncthreads();
+        for (int k = 2; k <= P; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = tid; i < P; i += THREADS) {
+                    const int p = i ^ j;
+                    if (p > i) {
+                        const int u = s_list[i], v = s_list[p];
+                        if ((u > v) == ((i & k) == 0)) s_list[i] = v, s_list[p] = u;
+                    }
+                }
+                __syncthreads();
+            }
+    }
+}
+
+// a list longer than LDS: of the 256 boxes from `base` on, those that touch brick (bx, by, bz) go to s_list in
+// ascending order; returns their number
+__device__ __forceinline__ int gather_window(const int4 *__restrict__ box, int N, int base, int bx, int by, int bz,
+                                             int *s_list, int *s_wcnt) {
+    const int tid = threadIdx.x;
+    const int n = base + tid;
+    bool hit = false;
+    if (n < N) {
+        const int4 bxy = box[2 * (size_t)n], bz_ = box[2 * (size_t)n + 1];
+        hit = bxy.x <= bx && bx <= bxy.y && bxy.z <= by && by <= bxy.w && bz_.x <= bz && bz <= bz_.y;
+    }
+    const unsigned long long mask = __ballot(hit);
+    __syncthreads();  // (s_wcnt and s_list of the previous window are no longer read)
+    if ((tid & 63) == 0) s_wcnt[tid >> 6] = __popcll(mask);
+    __syncthreads();
+    int before = 0, count = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; w++) {
+        const int c = s_wcnt[w];
+        if (w < (tid >> 6)) before += c;
+        count += c;
+    }
+    if (hit) s_list[before + __popcll(mask & ((1ull << (tid & 63)) - 1ull))] = n;
+    return count;
+}
+
+// term(p0, p1, p2, p3) for the records of the Gaussians s_list[0 .. count), in that order, staged 64 at a time through
+// s_rec with mu replaced by (ox, oy, oz) - mu, taken in fp64 and rounded once
+template <class Term>
+__device__ __forceinline__ void for_each_record(const float4 *__restrict__ rec, const int *s_list, int count, double ox,
+                                                double oy, double oz, float4 *s_rec, Term &&term) {
+    const int tid = threadIdx.x;
+    for (int c0 = 0; c0 < count; c0 += REC_CHUNK) {
+        const int m = min(REC_CHUNK, count - c0);
+        __syncthreads();  // s_list is written; the previous chunk's records are consumed
+        if ((tid >> 2) < m) {
+            const int q = tid & 3;
+            float4 v = rec[(size_t)s_list[c0 + (tid >> 2)] * REC_F4 + q];
+            if (q == 0) {
+                v.x = (float)(ox - (double)v.x);
+                v.y = (float)(oy - (double)v.y);
+                v.z = (float)(oz - (double)v.z);
+            }
+            s_rec[(tid >> 2) * REC_F4 + q] = v;
+        }
+        __syncthreads();
+        for (int r = 0; r < m; r++)
+            term(s_rec[r * REC_F4], s_rec[r * REC_F4 + 1], s_rec[r * REC_F4 + 2], s_rec[r * REC_F4 + 3]);
+    }
+}
+
 __global__ __launch_bounds__(THREADS) void k_mesh_density(Grid gr, int N, const float4 *__restrict__ rec,
                                                           const int4 *__restrict__ box, const int *__restrict__ offs,
                                                           const int *__restrict__ cur, const int *__restrict__ lists,
@@ -227,43 +337,24 @@ __global__ __launch_bounds__(THREADS) void k_mesh_density(Grid gr, int N, const 
     NodeAcc acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     const bool poison = *total > capacity;  // (uniform)
 
-    // accumulate the `count` Gaussians s_list[0 .. count) (ascending) into acc; every thread calls it (barriers inside)
-    auto consume = [&](int count) {
-        for (int c0 = 0; c0 < count; c0 += REC_CHUNK) {
-            const int m = min(REC_CHUNK, count - c0);
-            __syncthreads();  // s_list is written; the previous chunk's records are consumed
-            if ((tid >> 2) < m) {
-                const int q = tid & 3;
-                float4 v = rec[(size_t)s_list[c0 + (tid >> 2)] * REC_F4 + q];
-                if (q == 0) {
-                    v.x = (float)(ox - (double)v.x);
-                    v.y = (float)(oy - (double)v.y);
-                    v.z = (float)(oz - (double)v.z);
-                }
-                s_rec[(tid >> 2) * REC_F4 + q] = v;
-            }
-            __syncthreads();
-            for (int r = 0; r < m; r++) {
-                const float4 p0 = s_rec[r * REC_F4], p1 = s_rec[r * REC_F4 + 1], p2 = s_rec[r * REC_F4 + 2],
-                             p3 = s_rec[r * REC_F4 + 3];
-                const float dy = fmaf(fj, gr.h[1], p0.y), dz = fmaf(fk, gr.h[2], p0.z);
-                // the part of y that the thread's two nodes share
-                const float c0y = fmaf(p1.y, dz, p1.x * dy);  // row 0: A01 dy + A02 dz
-                const float c1y = fmaf(p2.x, dz, p1.w * dy);  // row 1: A11 dy + A12 dz
-                const float c2y = fmaf(p2.w, dz, p2.z * dy);  // row 2: A21 dy + A22 dz
+    // one Gaussian's term at the thread's two nodes
+    auto term = [&](const float4 p0, const float4 p1, const float4 p2, const float4 p3) {
+        const float dy = fmaf(fj, gr.h[1], p0.y), dz = fmaf(fk, gr.h[2], p0.z);
+        // the part of y that the thread's two nodes share
+        const float c0y = fmaf(p1.y, dz, p1.x * dy);  // row 0: A01 dy + A02 dz
+        const float c1y = fmaf(p2.x, dz, p1.w * dy);  // row 1: A11 dy + A12 dz
+        const float c2y = fmaf(p2.w, dz, p2.z * dy);  // row 2: A21 dy + A22 dz
 #pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const float dx = fmaf(k ? fi1 : fi0, gr.h[0], p0.x);
-                    const float y0 = fmaf(p0.w, dx, c0y), y1 = fmaf(p1.z, dx, c1y), y2 = fmaf(p2.y, dx, c2y);
-                    const float e = p3.x - fmaf(y2, y2, fmaf(y1, y1, y0 * y0));
-                    if (e >= log2eps) {
-                        const float w = __builtin_amdgcn_exp2f(e);
-                        acc[k].w += w;
-                        acc[k].r = fmaf(w, p3.y, acc[k].r);
-                        acc[k].g = fmaf(w, p3.z, acc[k].g);
-                        acc[k].b = fmaf(w, p3.w, acc[k].b);
-                    }
-                }
+        for (int k = 0; k < 2; k++) {
+            const float dx = fmaf(k ? fi1 : fi0, gr.h[0], p0.x);
+            const float y0 = fmaf(p0.w, dx, c0y), y1 = fmaf(p1.z, dx, c1y), y2 = fmaf(p2.y, dx, c2y);
+            const float e = p3.x - fmaf(y2, y2, fmaf(y1, y1, y0 * y0));
+            if (e >= log2eps) {
+                const float w = __builtin_amdgcn_exp2f(e);
+                acc[k].w += w;
+                acc[k].r = fmaf(w, p3.y, acc[k].r);
+                acc[k].g = fmaf(w, p3.z, acc[k].g);
+                acc[k].b = fmaf(w, p3.w, acc[k].b);
             }
         }
     };
@@ -271,57 +362,14 @@ __global__ __launch_bounds__(THREADS) void k_mesh_density(Grid gr, int N, const 
     const int L = cur[b];
     if (poison || L == 0) {
         // nothing to accumulate
-    } else if (L <= RANK_CAP && L <= SORT_CAP) {
-        // rank sort: the indices of a list are distinct, so the number of smaller ones is the place
-        int *tmp = s_list + RANK_CAP;
-        const int v = tid < L ? lists[(long long)offs[b] + tid] : 0x7fffffff;
-        tmp[tid] = v;
-        __syncthreads();
-        if (tid < L) {
-            int rank = 0;
-            for (int i = 0; i < L; i++) rank += tmp[i] < v;
-            s_list[rank] = v;
-        }
-        consume(L);
     } else if (L <= SORT_CAP) {
-        int P = RANK_CAP * 2;
-        while (P < L) P <<= 1;
-        for (int i = tid; i < P; i += THREADS) s_list[i] = i < L ? lists[(long long)offs[b] + i] : 0x7fffffff;
-        __syncthreads();
-        for (int k = 2; k <= P; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < P; i += THREADS) {
-                    const int p = i ^ j;
-                    if (p > i) {
-                        const int u = s_list[i], v = s_list[p];
-                        if ((u > v) == ((i & k) == 0)) s_list[i] = v, s_list[p] = u;
-                    }
-                }
-                __syncthreads();
-            }
-        consume(L);
+        order_list(lists + (long long)offs[b], L, s_list);
+        for_each_record(rec, s_list, L, ox, oy, oz, s_rec, term);
     } else {
-        // a list longer than LDS: walk all boxes in ascending order, 256 at a time, and keep those that touch this brick
+        // walk all boxes in ascending order, 256 at a time, and keep those that touch this brick
         for (int base = 0; base < N; base += THREADS) {
-            const int n = base + tid;
-            bool hit = false;
-            if (n < N) {
-                const int4 bxy = box[2 * (size_t)n], bz_ = box[2 * (size_t)n + 1];
-                hit = bxy.x <= bx && bx <= bxy.y && bxy.z <= by && by <= bxy.w && bz_.x <= bz && bz <= bz_.y;
-            }
-            const unsigned long long mask = __ballot(hit);
-            __syncthreads();  // (s_wcnt and s_list of the previous window are no longer read)
-            if ((tid & 63) == 0) s_wcnt[tid >> 6] = __popcll(mask);
-            __syncthreads();
-            int before = 0, count = 0;
-#pragma unroll
-            for (int w = 0; w < THREADS / 64; w++) {
-                const int c = s_wcnt[w];
-                if (w < (tid >> 6)) before += c;
-                count += c;
-            }
-            if (hit) s_list[before + __popcll(mask & ((1ull << (tid & 63)) - 1ull))] = n;
-            consume(count);
+            const int count = gather_window(box, N, base, bx, by, bz, s_list, s_wcnt);
+            for_each_record(rec, s_list, count, ox, oy, oz, s_rec, term);
         }
     }
 
@@ -339,6 +387,171 @@ __global__ __launch_bounds__(THREADS) void k_mesh_density(Grid gr, int N, const 
             rgb[3 * at + 1] = poison ? qnan : has ? acc[k].g / s : 0.f;
             rgb[3 * at + 2] = poison ? qnan : has ? acc[k].b / s : 0.f;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- sampling
+struct Domain {
+    double lo[3], hi[3];  // lo - h / 2 and lo + (G - 1/2) h in fp64: the points that are sampled
+};
+
+// per point: its brick (-1: not sampled; such a point's outputs are written here), one integer atomic on that brick
+__global__ __launch_bounds__(THREADS) void k_mesh_point_count(const float *__restrict__ pts, int M, Grid gr, Domain dom,
+                                                              const long long *__restrict__ total, long long capacity,
+                                                              int *__restrict__ pbrick, int *__restrict__ pcnt,
+                                                              float *__restrict__ sigma, float *__restrict__ rgb) {
+    const long long m = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (m >= M) return;
+    int bi[3];
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float p = pts[3 * m + a];
+        in = in && finite_f(p) && (double)p >= dom.lo[a] && (double)p <= dom.hi[a];
+        const double u = ((double)p - (double)gr.lo[a]) / (double)gr.h[a];  // the fp64 node coordinate
+        bi[a] = in ? min((int)floor(fmax(u, 0.0)), gr.G[a] - 1) / BR : 0;
+    }
+    int b = -1;
+    if (in) {
+        b = (bi[0] * gr.nb[1] + bi[1]) * gr.nb[2] + bi[2];
+        atomicAdd(&pcnt[b], 1);
+    } else {
+        const float v = *total > capacity ? __builtin_nanf("") : 0.f;
+        sigma[m] = v;
+        if (rgb) rgb[3 * m] = v, rgb[3 * m + 1] = v, rgb[3 * m + 2] = v;
+    }
+    pbrick[m] = b;
+}
+
+__global__ __launch_bounds__(THREADS) void k_mesh_point_fill(int M, const int *__restrict__ pbrick,
+                                                             const int *__restrict__ poffs, int *__restrict__ pcur,
+                                                             int *__restrict__ plist) {
+    const long long m = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (m >= M) return;
+    const int b = pbrick[m];
+    if (b < 0) return;
+    const long long at = (long long)poffs[b] + atomicAdd(&pcur[b], 1);
+    if (at >= 0 && at < M) plist[at] = (int)m;  // (the sampled points are at most M: always true)
+}
+
+// one workgroup per brick: its points, 256 at a time and one per thread, against its list in ascending order
+__global__ __launch_bounds__(THREADS) void k_mesh_sample(Grid gr, int N, const float4 *__restrict__ rec,
+                                                         const int4 *__restrict__ box, const int *__restrict__ offs,
+                                                         const int *__restrict__ cur, const int *__restrict__ lists,
+                                                         const long long *__restrict__ total, long long capacity,
+                                                         float log2eps, const float *__restrict__ pts,
+                                                         const int *__restrict__ poffs, const int *__restrict__ pcur,
+                                                         const int *__restrict__ plist, float *__restrict__ sigma,
+                                                         float *__restrict__ rgb) {
+    __shared__ int s_list[SORT_LDS];
+    __shared__ float4 s_rec[REC_CHUNK * REC_F4];
+    __shared__ int s_wcnt[THREADS / 64];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int P = pcur[b];
+    if (P == 0) return;  // (uniform)
+    const int bz = b % gr.nb[2], by = (b / gr.nb[2]) % gr.nb[1], bx = b / (gr.nb[2] * gr.nb[1]);
+    // the brick's first node, in fp64: a point and a record's mu are both subtracted from it before rounding to fp32
+    const double ox = (double)gr.lo[0] + (double)(bx * BR) * (double)gr.h[0];
+    const double oy = (double)gr.lo[1] + (double)(by * BR) * (double)gr.h[1];
+    const double oz = (double)gr.lo[2] + (double)(bz * BR) * (double)gr.h[2];
+    const bool poison = *total > capacity;  // (uniform)
+    const int L = cur[b];
+    const bool walk = !poison && L > 0 && L > SORT_CAP;
+    if (!poison && L > 0 && !walk) order_list(lists + (long long)offs[b], L, s_list);
+    const long long first = poffs[b];
+    const float qnan = __builtin_nanf("");
+
+    for (int p0 = 0; p0 < P; p0 += THREADS) {
+        const int m = p0 + tid < P ? plist[first + p0 + tid] : -1;
+        float lx = 0.f, ly = 0.f, lz = 0.f;
+        if (m >= 0) {
+            lx = (float)((double)pts[3 * (size_t)m] - ox);
+            ly = (float)((double)pts[3 * (size_t)m + 1] - oy);
+            lz = (float)((double)pts[3 * (size_t)m + 2] - oz);
+        }
+        NodeAcc acc = {0.f, 0.f, 0.f, 0.f};
+        // one Gaussian's term at the thread's point: k_mesh_density's, with the point in the place of the node
+        auto term = [&](const float4 q0, const float4 q1, const float4 q2, const float4 q3) {
+            const float dx = lx + q0.x, dy = ly + q0.y, dz = lz + q0.z;
+            const float y0 = fmaf(q0.w, dx, fmaf(q1.y, dz, q1.x * dy));
+            const float y1 = fmaf(q1.z, dx, fmaf(q2.x, dz, q1.w * dy));
+            const float y2 = fmaf(q2.y, dx, fmaf(q2.w, dz, q2.z * dy));
+            const float e = q3.x - fmaf(y2, y2, fmaf(y1, y1, y0 * y0));
+            if (e >= log2eps) {
+                const float w = __builtin_amdgcn_exp2f(e);
+                acc.w += w;
+                acc.r = fmaf(w, q3.y, acc.r);
+                acc.g = fmaf(w, q3.z, acc.g);
+                acc.b = fmaf(w, q3.w, acc.b);
+            }
+        };
+        if (walk) {
+            for (int base = 0; base < N; base += THREADS) {
+                const int count = gather_window(box, N, base, bx, by, bz, s_list, s_wcnt);
+                for_each_record(rec, s_list, count, ox, oy, oz, s_rec, term);
+            }
+        } else if (!poison && L > 0) {
+            for_each_record(rec, s_list, L, ox, oy, oz, s_rec, term);
+        }
+        if (m < 0) continue;
+        const float s = acc.w;
+        sigma[m] = poison ? qnan : s;
+        if (rgb) {
+            const bool has = s > 0.f;
+            rgb[3 * (size_t)m] = poison ? qnan : has ? acc.r / s : 0.f;
+            rgb[3 * (size_t)m + 1] = poison ? qnan : has ? acc.g / s : 0.f;
+            rgb[3 * (size_t)m + 2] = poison ? qnan : has ? acc.b / s : 0.f;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- atlas
+// one thread per texel: block q of T x T texels for the quad of faces 2q and 2q + 1
+__global__ __launch_bounds__(THREADS) void k_mesh_atlas(const float *__restrict__ vertices, long long nv,
+                                                        const int *__restrict__ faces, long long nq, int T, int cols,
+                                                        int rows, float *__restrict__ points, float *__restrict__ uvs,
+                                                        int *__restrict__ face_uvs) {
+// every fp32 operation is rounded on its own (include/lgm_mesh.h)
+#pragma clang fp contract(off)
+    const long long n = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (n >= nq * T * T) return;
+    const long long q = n / (T * T);
+    const int r = (int)(n % (T * T)), j = r / T, i = r % T;
+    const int *f = faces + 6 * q;
+    const int a = f[0], b = f[1], c = f[2], a2 = f[3], d = f[4], e = f[5];
+    // outward (q0, q1, q2), (q0, q2, q3): c == d; flipped (q0, q2, q1), (q0, q3, q2): b == e
+    const bool outward = c == d, flipped = !outward && b == e;
+    const int q0 = a, q1 = outward ? b : c, q2 = outward ? c : b, q3 = outward ? e : d;
+    const bool ok = a == a2 && (outward || flipped) && q0 >= 0 && q0 < nv && q1 >= 0 && q1 < nv && q2 >= 0 &&
+                    q2 < nv && q3 >= 0 && q3 < nv;
+    const float s = (float)i / (float)(T - 1), t = (float)j / (float)(T - 1);
+    float *out = points + 3 * n;
+    if (ok) {
+        const bool up = s >= t;
+        const float w0 = up ? 1.f - s : 1.f - t, w1 = up ? s - t : t - s, w2 = up ? t : s;
+        const float *v0 = vertices + 3 * (size_t)q0, *v1 = vertices + 3 * (size_t)(up ? q1 : q3),
+                    *v2 = vertices + 3 * (size_t)q2;
+#pragma unroll
+        for (int k = 0; k < 3; k++) out[k] = w0 * v0[k] + w1 * v1[k] + w2 * v2[k];
+    } else {
+        out[0] = out[1] = out[2] = __builtin_nanf("");
+    }
+    if (r != 0) return;
+    const float x0 = (float)((q % cols) * T), y0 = (float)((q / cols) * T), W = (float)(cols * T), H = (float)(rows * T);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {  // q0, q1, q2, q3: corners (0, 0), (1, 0), (1, 1), (0, 1)
+        const int ca = (k == 1 || k == 2), cb = k >> 1;
+        const float x = x0 + 0.5f + (float)(ca * (T - 1)), y = y0 + 0.5f + (float)(cb * (T - 1));
+        uvs[8 * q + 2 * k] = x / W;
+        uvs[8 * q + 2 * k + 1] = 1.f - y / H;
+    }
+    const int u0 = (int)(4 * q);
+    int *fu = face_uvs + 6 * q;
+    if (!flipped) {
+        fu[0] = u0, fu[1] = u0 + 1, fu[2] = u0 + 2, fu[3] = u0, fu[4] = u0 + 2, fu[5] = u0 + 3;
+    } else {
+        fu[0] = u0, fu[1] = u0 + 2, fu[2] = u0 + 1, fu[3] = u0, fu[4] = u0 + 3, fu[5] = u0 + 2;
     }
 }
 
@@ -486,11 +699,12 @@ int make_grid(const char *who, int Gx, int Gy, int Gz, const float *lo, const fl
     return LGM_OK;
 }
 
+// (M >= 0: the sampling pass's workspace, with the arrays of its M points after the lists)
 struct DensityLayout {
-    size_t rec, box, cnt, cur, bsum, total, lists, bytes;
+    size_t rec, box, cnt, cur, bsum, total, lists, pcnt, pcur, pbsum, ptotal, pbrick, plist, bytes;
     long long nbricks;
 };
-DensityLayout density_layout(long long N, const Grid &gr, long long capacity) {
+DensityLayout density_layout(long long N, const Grid &gr, long long capacity, long long M = -1) {
     DensityLayout L;
     L.nbricks = (long long)gr.nb[0] * gr.nb[1] * gr.nb[2];
     size_t at = 0;
@@ -501,6 +715,15 @@ DensityLayout density_layout(long long N, const Grid &gr, long long capacity) {
     L.bsum = at, at += up256((size_t)tiles_of(L.nbricks) * sizeof(long long));
     L.total = at, at += 256;
     L.lists = at, at += up256((size_t)capacity * sizeof(int));
+    L.pcnt = L.pcur = L.pbsum = L.ptotal = L.pbrick = L.plist = at;
+    if (M >= 0) {
+        L.pcnt = at, at += up256((size_t)L.nbricks * sizeof(int));
+        L.pcur = at, at += up256((size_t)L.nbricks * sizeof(int));
+        L.pbsum = at, at += up256((size_t)tiles_of(L.nbricks) * sizeof(long long));
+        L.ptotal = at, at += 256;
+        L.pbrick = at, at += up256((size_t)M * sizeof(int));
+        L.plist = at, at += up256((size_t)M * sizeof(int));
+    }
     L.bytes = at;
     return L;
 }
@@ -514,10 +737,11 @@ int scan_in_place(int *a, long long n, long long *bsum, long long *total, hipStr
 }
 
 // the checks and the passes lgm_mesh_density_count and lgm_mesh_density share: records, boxes, brick counts, scan
-// (the total goes to total_dst, or into the workspace when that is null)
+// (the total goes to total_dst, or into the workspace when that is null). M >= 0: the sampling pass, whose boxes are
+// k_mesh_sample_bin_count's
 int density_front(const char *who, const float *g, long long N, float mod, int Gx, int Gy, int Gz, const float *lo,
                   const float *h, float cutoff, long long capacity, void *ws, size_t ws_bytes, Grid &gr,
-                  DensityLayout &L, long long *total_dst, hipStream_t st) {
+                  DensityLayout &L, long long *total_dst, hipStream_t st, long long M = -1) {
     const int rc = make_grid(who, Gx, Gy, Gz, lo, h, true, gr);
     if (rc) return rc;
     if (N < 0 || N >= I31 || capacity < 0 || capacity >= I31) {
@@ -532,7 +756,7 @@ int density_front(const char *who, const float *g, long long N, float mod, int G
         set_error("%s: null pointer (g, ws)", who);
         return LGM_E_INVALID;
     }
-    L = density_layout(N, gr, capacity);
+    L = density_layout(N, gr, capacity, M);
     if (ws_bytes < L.bytes) {
         set_error("%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.bytes);
         return LGM_E_WORKSPACE;
@@ -542,9 +766,13 @@ int density_front(const char *who, const float *g, long long N, float mod, int G
         set_error("%s: hipMemsetAsync failed", who);
         return LGM_E_HIP;
     }
-    if (N > 0)
+    if (N > 0 && M < 0)
         LGM_LAUNCH("k_mesh_bin_count", st,
                    (k_mesh_bin_count<<<(unsigned)((N + THREADS - 1) / THREADS), THREADS, 0, st>>>(
+                       g, (int)N, mod, gr, cutoff, (float4 *)(w + L.rec), (int4 *)(w + L.box), (int *)(w + L.cnt))));
+    if (N > 0 && M >= 0)
+        LGM_LAUNCH("k_mesh_sample_bin_count", st,
+                   (k_mesh_sample_bin_count<<<(unsigned)((N + THREADS - 1) / THREADS), THREADS, 0, st>>>(
                        g, (int)N, mod, gr, cutoff, (float4 *)(w + L.rec), (int4 *)(w + L.box), (int *)(w + L.cnt))));
     return scan_in_place((int *)(w + L.cnt), L.nbricks, (long long *)(w + L.bsum),
                          total_dst ? total_dst : (long long *)(w + L.total), st);
@@ -623,6 +851,123 @@ extern "C" int lgm_mesh_density(const float *g, long long N, float scale_modifie
                    gr, (int)N, (const float4 *)(w + L.rec), (const int4 *)(w + L.box), (const int *)(w + L.cnt),
                    (const int *)(w + L.cur), (const int *)(w + L.lists), (const long long *)(w + L.total), capacity,
                    log2f(cutoff), sigma, rgb)));
+    return LGM_OK;
+}
+
+extern "C" size_t lgm_mesh_sample_workspace_size(long long N, long long M, int Gx, int Gy, int Gz, long long capacity) {
+    using namespace lgm;
+    if (N < 0 || N >= I31 || M < 0 || 3 * M >= I31 || capacity < 0 || capacity >= I31 || !grid_ok(Gx, Gy, Gz)) return 0;
+    Grid gr;
+    gr.G[0] = Gx, gr.G[1] = Gy, gr.G[2] = Gz;
+    for (int a = 0; a < 3; a++) gr.nb[a] = (gr.G[a] + BR - 1) / BR;
+    return density_layout(N, gr, capacity, M).bytes;
+}
+
+extern "C" int lgm_mesh_sample_count(const float *g, long long N, float scale_modifier, int Gx, int Gy, int Gz,
+                                     const float *lo, const float *h, float cutoff, void *ws, size_t ws_bytes,
+                                     long long *npairs, void *stream, const lgm_diag *diag) {
+    using namespace lgm;
+    clear_error();
+    DiagScope ds(diag);
+    hipStream_t st = (hipStream_t)stream;
+    Grid gr;
+    DensityLayout L;
+    if (!npairs) {
+        set_error("lgm_mesh_sample_count: null pointer (npairs)");
+        return LGM_E_INVALID;
+    }
+    return density_front("lgm_mesh_sample_count", g, N, scale_modifier, Gx, Gy, Gz, lo, h, cutoff, 0, ws, ws_bytes, gr, L,
+                         npairs, st, 0);
+}
+
+extern "C" int lgm_mesh_sample(const float *g, long long N, float scale_modifier, int Gx, int Gy, int Gz,
+                               const float *lo, const float *h, float cutoff, long long capacity, const float *points,
+                               long long M, float *sigma, float *rgb, void *ws, size_t ws_bytes, void *stream,
+                               const lgm_diag *diag) {
+    using namespace lgm;
+    clear_error();
+    DiagScope ds(diag);
+    const char *who = "lgm_mesh_sample";
+    hipStream_t st = (hipStream_t)stream;
+    Grid gr;
+    DensityLayout L;
+    if (M < 0 || 3 * M >= I31) {
+        set_error("%s: M=%lld: must be >= 0 with 3 M below 2^31", who, M);
+        return LGM_E_INVALID;
+    }
+    if (M > 0 && (!points || !sigma)) {
+        set_error("%s: null pointer (points, sigma)", who);
+        return LGM_E_INVALID;
+    }
+    const int rc = density_front(who, g, N, scale_modifier, Gx, Gy, Gz, lo, h, cutoff, capacity, ws, ws_bytes, gr, L,
+                                 nullptr, st, M);
+    if (rc || M == 0) return rc;
+    char *w = (char *)ws;
+    if (hipMemsetAsync(w + L.pcnt, 0, L.pbsum - L.pcnt, st) != hipSuccess) {  // (the points' counts and cursors)
+        set_error("%s: hipMemsetAsync failed", who);
+        return LGM_E_HIP;
+    }
+    if (N > 0)
+        LGM_LAUNCH("k_mesh_bin_fill", st,
+                   (k_mesh_bin_fill<<<(unsigned)((N + THREADS - 1) / THREADS), THREADS, 0, st>>>(
+                       (int)N, gr, (const int4 *)(w + L.box), (const int *)(w + L.cnt), (int *)(w + L.cur),
+                       (int *)(w + L.lists), capacity)));
+    Domain dom;
+    for (int a = 0; a < 3; a++) {
+        dom.lo[a] = (double)gr.lo[a] - (double)gr.h[a] / 2.0;
+        dom.hi[a] = (double)gr.lo[a] + ((double)gr.G[a] - 0.5) * (double)gr.h[a];
+    }
+    const unsigned pblocks = (unsigned)((M + THREADS - 1) / THREADS);
+    LGM_LAUNCH("k_mesh_point_count", st,
+               (k_mesh_point_count<<<pblocks, THREADS, 0, st>>>(points, (int)M, gr, dom, (const long long *)(w + L.total),
+                                                                capacity, (int *)(w + L.pbrick), (int *)(w + L.pcnt),
+                                                                sigma, rgb)));
+    const int rs = scan_in_place((int *)(w + L.pcnt), L.nbricks, (long long *)(w + L.pbsum),
+                                 (long long *)(w + L.ptotal), st);
+    if (rs) return rs;
+    LGM_LAUNCH("k_mesh_point_fill", st,
+               (k_mesh_point_fill<<<pblocks, THREADS, 0, st>>>((int)M, (const int *)(w + L.pbrick),
+                                                               (const int *)(w + L.pcnt), (int *)(w + L.pcur),
+                                                               (int *)(w + L.plist))));
+    LGM_LAUNCH("k_mesh_sample", st,
+               (k_mesh_sample<<<(unsigned)L.nbricks, THREADS, 0, st>>>(
+                   gr, (int)N, (const float4 *)(w + L.rec), (const int4 *)(w + L.box), (const int *)(w + L.cnt),
+                   (const int *)(w + L.cur), (const int *)(w + L.lists), (const long long *)(w + L.total), capacity,
+                   log2f(cutoff), points, (const int *)(w + L.pcnt), (const int *)(w + L.pcur),
+                   (const int *)(w + L.plist), sigma, rgb)));
+    return LGM_OK;
+}
+
+extern "C" int lgm_mesh_atlas(const float *vertices, long long nv, const int *faces, long long nf, int T, int cols,
+                              int rows, float *points, float *uvs, int *face_uvs, void *stream, const lgm_diag *diag) {
+    using namespace lgm;
+    clear_error();
+    DiagScope ds(diag);
+    const char *who = "lgm_mesh_atlas";
+    const long long nq = nf / 2;
+    if (nv < 0 || nf < 0 || (nf & 1) || 3 * nv >= I31 || 3 * nf >= I31) {
+        set_error("%s: nv=%lld nf=%lld: counts must be >= 0 with 3 x count below 2^31, nf even", who, nv, nf);
+        return LGM_E_INVALID;
+    }
+    if (T < 2 || cols < 1 || rows < 1 || (long long)cols * T > LGM_MESH_ATLAS_MAX ||
+        (long long)rows * T > LGM_MESH_ATLAS_MAX || (long long)cols * rows < nq) {
+        set_error("%s: T=%d cols=%d rows=%d for %lld quads: T >= 2, cols rows >= the quads, cols T and rows T <= %d",
+                  who, T, cols, rows, nq, LGM_MESH_ATLAS_MAX);
+        return LGM_E_INVALID;
+    }
+    if (3 * nq * T * T >= I31) {
+        set_error("%s: %lld quads of %d x %d texels: 3 x texels must be below 2^31", who, nq, T, T);
+        return LGM_E_INVALID;
+    }
+    if (nq > 0 && (!vertices || !faces || !points || !uvs || !face_uvs)) {
+        set_error("%s: null pointer (vertices, faces, points, uvs, face_uvs)", who);
+        return LGM_E_INVALID;
+    }
+    if (nq == 0) return LGM_OK;
+    hipStream_t st = (hipStream_t)stream;
+    LGM_LAUNCH("k_mesh_atlas", st,
+               (k_mesh_atlas<<<(unsigned)((nq * T * T + THREADS - 1) / THREADS), THREADS, 0, st>>>(
+                   vertices, nv, faces, nq, T, cols, rows, points, uvs, face_uvs)));
     return LGM_OK;
 }
 

@@ -6,8 +6,11 @@ nothing is random: two calls on the same input give the same bits.
 
   density_grid       Gaussians [N, 14] -> sigma [Gx, Gy, Gz], rgb [Gx, Gy, Gz, 3]
   extract_surface    sigma (and rgb) -> Mesh
-  gaussians_to_mesh  both, after save_ply's opacity prune
-  Mesh               vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 or None; save_obj, save_ply
+  gaussians_to_mesh  both, after save_ply's opacity prune (texels=T: bake_texture too)
+  sample_field       Gaussians, points [..., 3] -> sigma [...], rgb [..., 3]: the same field at arbitrary points
+  bake_texture       Mesh, Gaussians -> Mesh with a per-quad UV atlas and the Gaussians' colour at every texel
+  Mesh               vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 or None, and optionally
+                     uvs [4 Nq, 2], face_uvs [Nf, 3] int32, texture [H, W, 3] float32; save_obj, save_ply
 
 GPU tensors run the kernels of lgm_amd/csrc/mesh.hip (a missing library raises NativeError); CPU tensors take the
 vectorised torch forms of the same formulas below. `resolution = 256` is convert.py's grid size; `iso = 0.5` is a
@@ -16,7 +19,9 @@ choice, not a tuned value: no checkpoint exists offline, so neither default has 
 from __future__ import annotations
 
 import ctypes
-from dataclasses import dataclass
+import math
+import os
+from dataclasses import dataclass, replace
 from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -27,6 +32,7 @@ from ._native import ptr
 from .ply import write_mesh_ply
 
 CUTOFF = 1e-4  # include/lgm_mesh.h LGM_MESH_CUTOFF
+ATLAS_MAX = 16384  # include/lgm_mesh.h LGM_MESH_ATLAS_MAX
 # the 12 edges of a cell in include/lgm_mesh.h's order: (lower corner, axis); corner c = 4 di + 2 dj + dk
 _EDGES = ((0, 2), (0, 1), (0, 0), (1, 1), (1, 0), (2, 2), (2, 0), (3, 0), (4, 2), (4, 1), (5, 1), (6, 2))
 
@@ -53,10 +59,14 @@ def _c3(a: np.ndarray):
 @dataclass
 class Mesh:
     """A triangle mesh with per-vertex colours (tensors on the device that made them). Faces are wound so that
-    normals point out of the dense side."""
+    normals point out of the dense side. bake_texture adds the atlas: uvs [4 Nq, 2], face_uvs [Nf, 3] (per face corner,
+    the row of uvs) and texture [H, W, 3], row 0 at the top (v = 1)."""
     vertices: torch.Tensor
     faces: torch.Tensor
     colors: Optional[torch.Tensor] = None
+    uvs: Optional[torch.Tensor] = None
+    face_uvs: Optional[torch.Tensor] = None
+    texture: Optional[torch.Tensor] = None
 
     def _numpy(self):
         v = self.vertices.detach().cpu().numpy().astype(np.float32)
@@ -66,16 +76,38 @@ class Mesh:
 
     def save_obj(self, path: str) -> None:
         """Wavefront OBJ: `v x y z r g b` (the common vertex-colour extension; plain `v x y z` without colours) and
-        1-based `f a b c` lines."""
+        1-based `f a b c` lines. With a texture: `v x y z`, `vt u v`, `f a/ta b/tb c/tc`, and next to the file a .mtl
+        whose map_Kd names a .png of the texture (round(clip(c, 0, 1) 255), row 0 at the top)."""
         v, f, c = self._numpy()
+        if self.texture is not None:
+            return self._save_obj_textured(path, v, f)
         rows = v if c is None else np.concatenate([v, np.clip(c, 0.0, 1.0)], axis=1)
         with open(path, "w") as out:
             out.write(f"# {len(v)} vertices, {len(f)} faces\n")
             out.write("".join("v " + " ".join(repr(float(x)) for x in row) + "\n" for row in rows))
             out.write("".join(f"f {a + 1} {b + 1} {c_ + 1}\n" for a, b, c_ in f.tolist()))
 
+    def _save_obj_textured(self, path: str, v: np.ndarray, f: np.ndarray) -> None:
+        from PIL import Image
+        stem = os.path.splitext(path)[0]
+        name = os.path.basename(stem)
+        uv = self.uvs.detach().cpu().numpy().astype(np.float32)
+        fu = self.face_uvs.detach().cpu().numpy().astype(np.int32)
+        tex = self.texture.detach().cpu().numpy().astype(np.float32)
+        Image.fromarray(np.round(np.clip(tex, 0.0, 1.0) * 255.0).astype(np.uint8)).save(stem + ".png")
+        with open(stem + ".mtl", "w") as out:
+            out.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+        with open(path, "w") as out:
+            out.write(f"# {len(v)} vertices, {len(f)} faces, texture {tex.shape[1]} x {tex.shape[0]}\n")
+            out.write(f"mtllib {name}.mtl\nusemtl {name}\n")
+            out.write("".join("v " + " ".join(repr(float(x)) for x in row) + "\n" for row in v))
+            out.write("".join("vt " + " ".join(repr(float(x)) for x in row) + "\n" for row in uv))
+            out.write("".join(f"f {a + 1}/{ta + 1} {b + 1}/{tb + 1} {c_ + 1}/{tc + 1}\n"
+                              for (a, b, c_), (ta, tb, tc) in zip(f.tolist(), fu.tolist())))
+
     def save_ply(self, path: str) -> None:
-        """Binary little-endian PLY: float x y z (and uchar red green blue), faces as `list uchar int vertex_indices`."""
+        """Binary little-endian PLY: float x y z (and uchar red green blue), faces as `list uchar int vertex_indices`
+        (a texture is not written)."""
         v, f, c = self._numpy()
         write_mesh_ply(path, v, f, c)
 
@@ -178,6 +210,98 @@ def density_grid(gaussians: torch.Tensor, resolution: Union[int, Sequence[int]] 
     return sigma, rgb
 
 
+# ------------------------------------------------------------------------------------------------------- sampling
+def _sample_native(g, pts, G, lo, h, scale_modifier, cutoff, sigma, rgb):
+    dev = g.device
+    N, M = g.shape[0], pts.shape[0]
+    lo_c, h_c = _c3(lo), _c3(h)
+    with torch.cuda.device(dev):
+        ws0, _ = nat.workspace("lgm_mesh_sample_workspace_size", dev, N, 0, *G, 0)
+        npairs = torch.zeros(1, dtype=torch.int64, device=dev)
+        nat.call("lgm_mesh_sample_count", dev, ptr(g) if N else None, N, float(scale_modifier), *G, lo_c, h_c,
+                 float(cutoff), ptr(ws0), ws0.numel(), ptr(npairs))
+        cap = int(npairs.item())  # the lists' length is data dependent: the one host sync of the sampling pass
+        if cap >= 2 ** 31:
+            raise nat.NativeError(f"lgm_mesh_sample: {cap} (Gaussian, brick) pairs, the lists are indexed with 31 bits; "
+                                  "raise the cutoff or lower the resolution")
+        del ws0
+        ws, _ = nat.workspace("lgm_mesh_sample_workspace_size", dev, N, M, *G, cap)
+        nat.call("lgm_mesh_sample", dev, ptr(g) if N else None, N, float(scale_modifier), *G, lo_c, h_c, float(cutoff),
+                 cap, ptr(pts) if M else None, M, ptr(sigma) if M else None, ptr(rgb) if M else None, ptr(ws), ws.numel())
+
+
+def _sample_torch(g, pts, G, lo, h, scale_modifier, cutoff, sigma, rgb):
+    """include/lgm_mesh.h's sampling pass in fp64, vectorised: the sampled points in runs of ascending x against the
+    Gaussians whose box reaches the run."""
+    sigma.zero_()
+    if rgb is not None:
+        rgb.zero_()
+    lo64 = torch.from_numpy(np.asarray(lo, np.float32).astype(np.float64))
+    h64 = torch.from_numpy(np.asarray(h, np.float32).astype(np.float64))
+    top = torch.tensor([n - 0.5 for n in G], dtype=torch.float64)
+    X = pts.double()
+    inside = (torch.isfinite(X) & (X >= lo64 - h64 / 2.0) & (X <= lo64 + top * h64)).all(dim=1)
+    g = g.double()
+    fin = torch.isfinite(g).all(dim=1)
+    o, s, q = g[:, 3], g[:, 4:7] * float(scale_modifier), g[:, 7:11]
+    qn = q.norm(dim=1)
+    keep = fin & (o > cutoff) & (s > 0).all(dim=1) & (qn > 0)
+    g, o, s, q = g[keep], o[keep], s[keep], q[keep] / qn[keep, None]
+    sel = inside.nonzero().squeeze(1)
+    if g.shape[0] == 0 or sel.numel() == 0:
+        return
+    r, x, y, z = q.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+    A = R.transpose(1, 2) / s[:, :, None]  # diag(s)^-1 R^T
+    rho2 = 2.0 * torch.log(o / cutoff)
+    ext_x = torch.sqrt(rho2 * ((R[:, 0, :] * s) ** 2).sum(dim=1)) * (1 + 1e-9) + 1e-12
+    mu, c = g[:, 0:3], g[:, 11:14]
+    sel = sel[torch.argsort(X[sel, 0])]
+    for p0 in range(0, sel.numel(), 4096):
+        idx_p = sel[p0:p0 + 4096]
+        Xp = X[idx_p]
+        near = ((mu[:, 0] + ext_x >= Xp[0, 0]) & (mu[:, 0] - ext_x <= Xp[-1, 0])).nonzero().squeeze(1)
+        sw = torch.zeros(Xp.shape[0], dtype=torch.float64)
+        swc = torch.zeros(Xp.shape[0], 3, dtype=torch.float64)
+        for n0 in range(0, near.numel(), 256):
+            idx = near[n0:n0 + 256]
+            yv = torch.einsum("nka,pna->pnk", A[idx], Xp[:, None, :] - mu[idx][None])
+            d2 = (yv * yv).sum(dim=2)
+            w = torch.where(d2 <= rho2[idx][None], o[idx][None] * torch.exp(-0.5 * d2), torch.zeros((), dtype=d2.dtype))
+            sw += w.sum(dim=1)
+            swc += w @ c[idx]
+        sigma[idx_p] = sw.float()
+        if rgb is not None:
+            col = torch.where(sw[:, None] > 0, swc / sw.clamp_min(1e-300)[:, None], torch.zeros((), dtype=sw.dtype))
+            rgb[idx_p] = col.float()
+
+
+def sample_field(gaussians: torch.Tensor, points: torch.Tensor, resolution: Union[int, Sequence[int]] = 256,
+                 bound: float = 1.0, scale_modifier: float = 1.0, cutoff: float = CUTOFF, *, colors: bool = True):
+    """The Gaussians' density and colour at arbitrary points [..., 3] (include/lgm_mesh.h, sampling pass): density_grid's
+    formulas with x = the point. The grid of `resolution` nodes over [-bound, bound]^3 is only the acceleration
+    structure and the domain: a point with a non-finite coordinate or more than half a cell outside the box gets
+    sigma = 0, rgb = 0. Returns (sigma [...], rgb [..., 3]) float32 on the Gaussians' device, rgb None with
+    colors=False."""
+    g = _check_gaussians(gaussians)
+    G, lo, h = grid_params(resolution, bound)
+    if not (cutoff > 0 and np.isfinite(cutoff)) or not np.isfinite(scale_modifier):
+        raise ValueError(f"cutoff {cutoff} must be positive and finite, scale_modifier {scale_modifier} finite")
+    if points.dim() < 1 or points.shape[-1] != 3 or points.device != g.device:
+        raise ValueError(f"points of shape {tuple(points.shape)} on {points.device}: expected [..., 3] on {g.device}")
+    lead = tuple(points.shape[:-1])
+    pts = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    M = pts.shape[0]
+    if 3 * M >= 2 ** 31:
+        raise ValueError(f"{M} points: the kernels index 3 M with 31 bits; sample in parts")
+    sigma = torch.empty(M, dtype=torch.float32, device=g.device)
+    rgb = torch.empty(M, 3, dtype=torch.float32, device=g.device) if colors else None
+    (_sample_native if g.is_cuda else _sample_torch)(g, pts, G, lo, h, scale_modifier, cutoff, sigma, rgb)
+    return sigma.reshape(lead), (rgb.reshape(lead + (3,)) if colors else None)
+
+
 # ------------------------------------------------------------------------------------------------------- extraction
 def _extract_native(sigma, rgb, iso, G, lo, h) -> Mesh:
     dev = sigma.device
@@ -278,12 +402,121 @@ def extract_surface(sigma: torch.Tensor, rgb: Optional[torch.Tensor] = None, iso
     return (_extract_native if sigma.is_cuda else _extract_torch)(sigma, rgb, iso, G, lo, h)
 
 
+# ------------------------------------------------------------------------------------------------------- texture
+def atlas_shape(nq: int, texels: int):
+    """(cols, rows, W, H) of the atlas of nq quads at `texels` per quad edge: block q at column q % cols, row q // cols."""
+    cols = math.isqrt(nq - 1) + 1 if nq > 0 else 1  # ceil(sqrt(nq)), at least 1
+    rows = max(1, -(-nq // cols))
+    W, H = cols * texels, rows * texels
+    if W > ATLAS_MAX or H > ATLAS_MAX:
+        raise ValueError(f"{nq} quads at {texels} texels: a texture of {W} x {H}, more than {ATLAS_MAX} a side; lower "
+                         "texels or the mesh resolution")
+    return cols, rows, W, H
+
+
+def _check_quads(faces: torch.Tensor, nv: int) -> None:
+    """Faces 2q, 2q + 1 must be a quad of the extraction pass: (q0, q1, q2), (q0, q2, q3) or (q0, q2, q1), (q0, q3, q2)."""
+    nf = faces.shape[0]
+    if nf % 2:
+        raise ValueError(f"{nf} faces: a mesh of extract_surface has two per quad")
+    if nf == 0:
+        return
+    if int(faces.min()) < 0 or int(faces.max()) >= nv:
+        raise ValueError(f"face indices outside [0, {nv})")
+    p = faces.reshape(-1, 6)
+    good = (p[:, 0] == p[:, 3]) & ((p[:, 2] == p[:, 4]) | (p[:, 1] == p[:, 5]))
+    if not bool(good.all()):
+        raise ValueError(f"faces {2 * int((~good).nonzero()[0])} and the next are not the two triangles of a quad sharing "
+                         "its q0-q2 diagonal: bake_texture takes meshes of extract_surface")
+
+
+def _atlas_native(vertices, faces, T, cols, rows):
+    dev = vertices.device
+    nv, nf = vertices.shape[0], faces.shape[0]
+    nq = nf // 2
+    points = torch.empty(nq, T, T, 3, dtype=torch.float32, device=dev)
+    uvs = torch.empty(nq, 4, 2, dtype=torch.float32, device=dev)
+    face_uvs = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    if nq:
+        with torch.cuda.device(dev):
+            nat.call("lgm_mesh_atlas", dev, ptr(vertices), nv, ptr(faces), nf, T, cols, rows, ptr(points), ptr(uvs),
+                     ptr(face_uvs))
+    return points, uvs, face_uvs
+
+
+def _atlas_torch(vertices, faces, T, cols, rows):
+    """include/lgm_mesh.h's atlas in fp32 torch operations, each rounded on its own, in the header's order."""
+    nq = faces.shape[0] // 2
+    p = faces.reshape(-1, 6).long()
+    outward = p[:, 2] == p[:, 4]
+    q0, q1, q2 = p[:, 0], torch.where(outward, p[:, 1], p[:, 2]), torch.where(outward, p[:, 2], p[:, 1])
+    q3 = torch.where(outward, p[:, 5], p[:, 4])
+    v0, v1, v2, v3 = (vertices[q][:, None, None, :] for q in (q0, q1, q2, q3))
+    ramp = torch.arange(T, dtype=torch.float32) / torch.tensor(float(T - 1), dtype=torch.float32)
+    s, t = ramp[None, :].expand(T, T), ramp[:, None].expand(T, T)  # [j, i]: s along i, t along j
+    up = s >= t
+    one = torch.ones((), dtype=torch.float32)
+    w0, w1, w2 = torch.where(up, one - s, one - t), torch.where(up, s - t, t - s), torch.where(up, t, s)
+    vm = torch.where(up[None, :, :, None], v1, v3)
+    points = w0[None, :, :, None] * v0 + w1[None, :, :, None] * vm + w2[None, :, :, None] * v2
+    q = torch.arange(nq)
+    x0, y0 = ((q % cols) * T).float(), ((q // cols) * T).float()
+    ca = torch.tensor([0.0, 1.0, 1.0, 0.0]) * float(T - 1)
+    cb = torch.tensor([0.0, 0.0, 1.0, 1.0]) * float(T - 1)
+    x, y = x0[:, None] + 0.5 + ca[None], y0[:, None] + 0.5 + cb[None]
+    uvs = torch.stack([x / float(cols * T), one - y / float(rows * T)], dim=2)
+    k = torch.where(outward[:, None], torch.tensor([[0, 1, 2, 0, 2, 3]]), torch.tensor([[0, 2, 1, 0, 3, 2]]))
+    face_uvs = (4 * q[:, None] + k).reshape(-1, 3).to(torch.int32)
+    return points.contiguous(), uvs.contiguous(), face_uvs
+
+
+def mesh_atlas(mesh: Mesh, texels: int = 4):
+    """The per-quad atlas of a mesh of extract_surface (include/lgm_mesh.h, atlas): (points [Nq, T, T, 3] with texel
+    (i, j) at [q, j, i], uvs [Nq, 4, 2], face_uvs [Nf, 3] int32, (cols, rows, W, H)). Raises ValueError on a mesh
+    whose faces are not such quads."""
+    T = int(texels)
+    if T < 2:
+        raise ValueError(f"texels {texels}: at least 2 per quad edge")
+    vertices = mesh.vertices.detach().to(torch.float32).contiguous()
+    faces = mesh.faces.detach().to(torch.int32).contiguous()
+    if faces.device != vertices.device:
+        raise ValueError(f"faces on {faces.device}, vertices on {vertices.device}")
+    _check_quads(faces, vertices.shape[0])
+    shape = atlas_shape(faces.shape[0] // 2, T)
+    out = (_atlas_native if vertices.is_cuda else _atlas_torch)(vertices, faces, T, shape[0], shape[1])
+    return out + (shape,)
+
+
+def bake_texture(mesh: Mesh, gaussians: torch.Tensor, texels: int = 4, bound: float = 1.0, scale_modifier: float = 1.0,
+                 cutoff: float = CUTOFF, resolution: Union[int, Sequence[int]] = 256) -> Mesh:
+    """A mesh of extract_surface with a texture evaluated directly from the Gaussians: every quad (faces 2q, 2q + 1)
+    gets a block of texels x texels texels whose 3D points lie on its two triangles, and the texture is sample_field's
+    rgb there, so colour detail does not depend on the mesh's resolution. Nothing is fitted; two calls give the same
+    bits. Returns the same vertices, faces and colours with uvs [4 Nq, 2], face_uvs [Nf, 3] and texture [H, W, 3]
+    (row 0 at the top; blocks past the last quad are zero). `resolution` is sample_field's acceleration grid."""
+    g = _check_gaussians(gaussians)
+    if g.device != mesh.vertices.device:
+        raise ValueError(f"gaussians on {g.device}, mesh on {mesh.vertices.device}")
+    points, uvs, face_uvs, (cols, rows, W, H) = mesh_atlas(mesh, texels)
+    T, nq = int(texels), points.shape[0]
+    _, rgb = sample_field(g, points, resolution, bound, scale_modifier, cutoff)
+    blocks = torch.zeros(rows * cols, T, T, 3, dtype=torch.float32, device=g.device)
+    blocks[:nq] = rgb
+    texture = blocks.reshape(rows, cols, T, T, 3).permute(0, 2, 1, 3, 4).reshape(H, W, 3).contiguous()
+    return replace(mesh, uvs=uvs.reshape(-1, 2), face_uvs=face_uvs, texture=texture)
+
+
 def gaussians_to_mesh(gaussians: torch.Tensor, resolution: Union[int, Sequence[int]] = 256, iso: float = 0.5,
-                      bound: float = 1.0, min_opacity: float = 0.005, scale_modifier: float = 1.0) -> Mesh:
+                      bound: float = 1.0, min_opacity: float = 0.005, scale_modifier: float = 1.0,
+                      texels: Optional[int] = None) -> Mesh:
     """Gaussians [N, 14] or [1, N, 14] -> a closed, coloured triangle mesh: save_ply's opacity prune (>= min_opacity),
     density_grid, extract_surface. resolution = 256 is convert.py's grid; iso = 0.5 is a choice, not a tuned value (no
-    trained checkpoint exists offline to tune it on)."""
+    trained checkpoint exists offline to tune it on). texels = T: bake_texture of the pruned Gaussians on that mesh,
+    T texels per quad edge (colour detail then no longer depends on the resolution)."""
     g = _check_gaussians(gaussians)
     g = g[g[:, 3] >= min_opacity]
     sigma, rgb = density_grid(g, resolution, bound, scale_modifier)
-    return extract_surface(sigma, rgb, iso, bound)
+    mesh = extract_surface(sigma, rgb, iso, bound)
+    if texels is None:
+        return mesh
+    return bake_texture(mesh, g, texels, bound, scale_modifier, resolution=resolution)

@@ -7,7 +7,13 @@
                     (--baseline-resolution^3 x --baseline-n, 64^3 x 4,096), next to the kernels at that size: there
                     is no earlier implementation to time
 
-    python scripts/bench_mesh.py [--resolution 256] [--n 65536] [--iters 20] [--warmup 3]
+  --texels T        also the textured export at T texels per quad edge (off by default: the output above is then
+                    unchanged): mesh_atlas (atlas_ms), sample_field at the atlas points (sample_ms, per kernel too) and
+                    the whole bake_texture (texture_ms) on the mesh above, with the point count and the (Gaussian,
+                    brick) pairs; and, at the baseline's size, sample_field next to the same formulas as dense,
+                    chunked fp32 torch operations over the same points (sample_torch_ms)
+
+    python scripts/bench_mesh.py [--resolution 256] [--n 65536] [--iters 20] [--warmup 3] [--texels 4]
 
 Times are host-clock around work that ends in a device synchronise, after warm-up; the per-kernel times come from HIP
 events around each launch in separate iterations (profiling slows the host side).
@@ -52,9 +58,10 @@ def kernels(fn, iters: int) -> dict:
     return out
 
 
-def dense_torch_density(g: torch.Tensor, G, lo, h, cutoff: float = 1e-4):
+def dense_torch_density(g: torch.Tensor, G, lo, h, cutoff: float = 1e-4, X: torch.Tensor = None):
     """include/lgm_mesh.h's density by dense fp32 torch operations on g's device: every node against every Gaussian,
-    in chunks of 32,768 nodes x 256 Gaussians."""
+    in chunks of 32,768 nodes x 256 Gaussians. X [M, 3]: those points instead of the grid's nodes (sigma [M],
+    rgb [M, 3])."""
     o, s, q = g[:, 3], g[:, 4:7], g[:, 7:11]
     q = q / q.norm(dim=1, keepdim=True)
     r, x, y, z = q.unbind(1)
@@ -64,8 +71,10 @@ def dense_torch_density(g: torch.Tensor, G, lo, h, cutoff: float = 1e-4):
     A = R.transpose(1, 2) / s[:, :, None]
     rho2 = 2.0 * torch.log(o / cutoff)
     mu, c = g[:, 0:3], g[:, 11:14]
-    ax = [float(lo[a]) + torch.arange(G[a], device=g.device, dtype=torch.float32) * float(h[a]) for a in range(3)]
-    X = torch.stack(torch.meshgrid(*ax, indexing="ij"), dim=-1).reshape(-1, 3)
+    given = X is not None
+    if X is None:
+        ax = [float(lo[a]) + torch.arange(G[a], device=g.device, dtype=torch.float32) * float(h[a]) for a in range(3)]
+        X = torch.stack(torch.meshgrid(*ax, indexing="ij"), dim=-1).reshape(-1, 3)
     sw = torch.zeros(X.shape[0], device=g.device)
     swc = torch.zeros(X.shape[0], 3, device=g.device)
     for p0 in range(0, X.shape[0], 32768):
@@ -77,7 +86,42 @@ def dense_torch_density(g: torch.Tensor, G, lo, h, cutoff: float = 1e-4):
             w = torch.where(d2 <= rho2[sl][None], o[sl][None] * torch.exp(-0.5 * d2), torch.zeros((), device=g.device))
             sw[p0:p0 + 32768] += w.sum(dim=1)
             swc[p0:p0 + 32768] += w @ c[sl]
+    if given:
+        return sw, swc / sw.clamp_min(1e-30)[:, None]
     return sw.reshape(G), (swc / sw.clamp_min(1e-30)[:, None]).reshape(tuple(G) + (3,))
+
+
+def texture_section(M, g, mesh, gb, a, timed_, kernels_) -> dict:
+    """--texels: the textured export on `mesh` (of g at --resolution), and sample_field next to dense torch at the
+    baseline's size."""
+    from lgm_amd import _native as nat
+    T = a.texels
+    points, uvs, face_uvs, (cols, rows, W, H) = M.mesh_atlas(mesh, T)
+    G, lo, h = M.grid_params(a.resolution)
+    ws, _ = nat.workspace("lgm_mesh_sample_workspace_size", g.device, g.shape[0], 0, *G, 0)
+    npairs = torch.zeros(1, dtype=torch.int64, device=g.device)
+    nat.call("lgm_mesh_sample_count", g.device, nat.ptr(g), g.shape[0], 1.0, *G, M._c3(lo), M._c3(h), M.CUTOFF,
+             nat.ptr(ws), ws.numel(), nat.ptr(npairs))
+    out = {"texels": T, "quads": int(points.shape[0]), "points": int(points.shape[0]) * T * T, "texture": [W, H],
+           "pairs": int(npairs.item()),
+           "atlas_ms": timed_(lambda: M.mesh_atlas(mesh, T), a.warmup, a.iters),
+           "sample_ms": timed_(lambda: M.sample_field(g, points, a.resolution), a.warmup, a.iters),
+           "texture_ms": timed_(lambda: M.bake_texture(mesh, g, T, resolution=a.resolution), a.warmup, a.iters),
+           "sample_kernels": kernels_(lambda: M.sample_field(g, points, a.resolution), a.iters),
+           "atlas_kernels": kernels_(lambda: M.mesh_atlas(mesh, T), a.iters)}
+    # the torch composition, at a size it can finish: the baseline's Gaussians and the atlas points of their own mesh
+    Gb, lo, h = M.grid_params(a.baseline_resolution)
+    mb = M.extract_surface(*M.density_grid(gb, Gb), a.iso)
+    pb = M.mesh_atlas(mb, T)[0].reshape(-1, 3)
+    ref_s, ref_c = dense_torch_density(gb, Gb, lo, h, X=pb)
+    our_s, our_c = M.sample_field(gb, pb, Gb)
+    seen = ref_s > 1e-3
+    out["baseline"] = {"resolution": a.baseline_resolution, "gaussians": int(gb.shape[0]), "points": int(pb.shape[0]),
+                       "max_abs_sigma_difference": float((ref_s - our_s).abs().max()),
+                       "max_abs_rgb_difference": float((ref_c - our_c)[seen].abs().max()) if bool(seen.any()) else 0.0,
+                       "sample_torch_ms": timed_(lambda: dense_torch_density(gb, Gb, lo, h, X=pb), 1, a.baseline_iters),
+                       "sample_ms": timed_(lambda: M.sample_field(gb, pb, Gb), a.warmup, a.iters)}
+    return out
 
 
 def main():
@@ -90,6 +134,7 @@ def main():
     ap.add_argument("--baseline-resolution", type=int, default=64)
     ap.add_argument("--baseline-n", type=int, default=4096)
     ap.add_argument("--baseline-iters", type=int, default=3)
+    ap.add_argument("--texels", type=int, default=None, help="also time the textured export at this many texels per quad edge")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mesh.py measures on the GPU: no GPU found")
@@ -119,6 +164,8 @@ def main():
                        "max_abs_sigma_difference": float((ref_s - our_s).abs().max()), "sigma_max": float(ref_s.max()),
                        "dense_torch": timed(lambda: dense_torch_density(gb, Gb, lo, h), 1, a.baseline_iters),
                        "density_grid": timed(lambda: M.density_grid(gb, Gb), a.warmup, a.iters)}
+    if a.texels is not None:
+        res["texture"] = texture_section(M, g, mesh, gb, a, timed, kernels)
     print(json.dumps(res))
 
 

@@ -32,12 +32,12 @@ def usage(src):
             out[-1][1][m.group(1)] = int(m.group(2))
     names = subprocess.run(["c++filt"], input="\n".join(n for n, _ in out), capture_output=True,
                            text=True).stdout.split("\n")
-    short = [re.sub(r"^void lgm::\(anonymous namespace\)::|\(.*", "", n) for n in names]
+    short = [re.sub(r"^(?:void )?lgm::\(anonymous namespace\)::|\(.*", "", n) for n in names]
     return [(s, u) for s, (_, u) in zip(short, out)]
 
 
 if __name__ == "__main__":
     rows = usage(os.path.join(B.HERE, sys.argv[1]))
     print(f"# {sys.argv[1]}: {len(rows)} kernels;", " | ".join(FIELDS))
-    for name, u in sorted(rows):
+    for name, u in sorted(rows, key=lambda row: row[0]):  # (two kernels may demangle to one short name)
         print(name, *(u[f] for f in FIELDS), sep="\t")

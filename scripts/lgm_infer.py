@@ -6,12 +6,13 @@ and N orbit frames through lgm_amd.cameras.render_orbit_frames. Runs on the GPU 
 
     python scripts/lgm_infer.py [--png tests/golden/catstatue_rgba.png] [--ckpt STATE_DICT.pt] [--frames 8]
                                 [--device cuda|cpu] [--bf16] [--native-conv] [--out bench_out_lgm_infer]
-                                [--mesh] [--mesh-resolution 256] [--mesh-iso 0.5]
+                                [--mesh] [--mesh-resolution 256] [--mesh-iso 0.5] [--mesh-texels N]
 
 --native-conv (with --bf16 on the GPU) runs the UNet's stride-1 convolutions on the HIP kernel (UNet.native_conv)
 instead of the library convolution: no first-call solver search.
 --mesh also writes object.obj next to the PLY (lgm_amd.mesh: the Gaussians' density on a grid, surface nets) and adds
-its vertex and face counts to the JSON line.
+its vertex and face counts to the JSON line. --mesh-texels N bakes a texture from the Gaussians at N texels per quad
+edge (object.mtl and object.png next to the OBJ) and adds its size to the JSON line.
 """
 from __future__ import annotations
 
@@ -43,6 +44,8 @@ def main():
     ap.add_argument("--mesh", action="store_true", help="also export a coloured triangle mesh (object.obj)")
     ap.add_argument("--mesh-resolution", type=int, default=256)
     ap.add_argument("--mesh-iso", type=float, default=0.5)
+    ap.add_argument("--mesh-texels", type=int, default=None,
+                    help="with --mesh: texels per quad edge of a texture baked from the Gaussians (default: vertex colours)")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -86,9 +89,12 @@ def main():
         if a.mesh:
             t0 = time.perf_counter()
             obj = os.path.join(a.out, "object.obj")
-            mesh = model.gs.save_mesh(gaussians.float(), obj, resolution=a.mesh_resolution, iso=a.mesh_iso)
+            mesh = model.gs.save_mesh(gaussians.float(), obj, resolution=a.mesh_resolution, iso=a.mesh_iso,
+                                      texels=a.mesh_texels)
             t["mesh_s"] = time.perf_counter() - t0
             mesh_info = {"mesh": obj, "mesh_vertices": int(mesh.vertices.shape[0]), "mesh_faces": int(mesh.faces.shape[0])}
+            if mesh.texture is not None:
+                mesh_info["mesh_texture"] = [int(mesh.texture.shape[1]), int(mesh.texture.shape[0])]  # W, H
         t0 = time.perf_counter()
         az = np.arange(a.frames, dtype=np.float64) * (360.0 / max(a.frames, 1))
         frames = render_orbit_frames(model.gs, gaussians, az, radius=opt.cam_radius).cpu().numpy()
