@@ -27,7 +27,7 @@ const char *lgm_last_error(void);
 
 /* ABI version (bumped on any signature change). 3: per-call lgm_diag, LGM_RENDER_NO_CULL as a per-call option.
  * 4: lgm_diag.det_limit_log2. 5: lgm_attn_workspace_size takes D. 6: lgm_gn_silu_* (lgm_norm.h).
- * 8: lgm_optim_* (lgm_optim.h). 10: lgm_mesh_* (lgm_mesh.h). */
+ * 8: lgm_optim_* (lgm_optim.h). 10: lgm_mesh_* (lgm_mesh.h). 11: lgm_meshraster_* (lgm_meshraster.h). */
 int lgm_abi_version(void);
 
 /* Profiler object: create, read per-kernel totals, reset, destroy. It records into itself only while a call is

@@ -117,6 +117,12 @@ SIGNATURES = {
     "lgm_mesh_count": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, _vp, _c_size, _vp, _vp, _vp]),
     "lgm_mesh_emit": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_size, _c_ll, _c_ll, _vp, _vp,
                                _vp, _c_ll, _c_ll, _vp, _vp]),
+    "lgm_meshraster_workspace_size": (_c_size, [_c_int, _c_ll, _c_ll, _c_int, _c_int, _c_int, _c_int]),
+    "lgm_meshraster_unit_log2": (_c_int, [_c_int, _c_int, _c_int]),
+    "lgm_meshraster_forward": (_c_int, [_vp, _c_ll, _vp, _c_ll, _vp, _c_ll, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int,
+                                        _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_size, _vp, _vp]),
+    "lgm_meshraster_backward": (_c_int, [_c_ll, _vp, _c_ll, _vp, _c_ll, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp,
+                                         _vp, _vp, _vp, _c_size, _vp, _vp]),
     "lgm_profiler_create": (_vp, []),
     "lgm_profiler_summary": (_c_int, [_vp, ctypes.c_char_p, _c_size]),
     "lgm_profiler_reset": (_c_int, [_vp]),
@@ -126,7 +132,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # include/lgm_attn.h LGM_ATTN_F32 / _BF16 / _F16
 RENDER_NO_CULL = 1  # include/lgm_render.h LGM_RENDER_NO_CULL
 RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(HERE)
 SOURCES = ["csrc/common.hip", "csrc/render_bin.hip", "csrc/render_raster.hip", "csrc/render_api.hip",
            "csrc/attention.hip", "csrc/head.hip", "csrc/mvattn.hip", "csrc/wgrad.hip", "csrc/gnsilu.hip",
            "csrc/lpips.hip", "csrc/data.hip", "csrc/optim.hip", "csrc/conv_wgrad.hip",
-           "csrc/conv_fwd.hip", "csrc/mesh.hip"]
+           "csrc/conv_fwd.hip", "csrc/mesh.hip", "csrc/meshraster.hip"]
 # per-source extra flags. attention.hip: no NaN semantics -- its max / exp chains then skip the quieting
 # canonicalisations clang inserts before every fmaxf of an MFMA result (the render kernels keep IEEE NaN handling:
 # degenerate-Gaussian tests such as !(det > 0) rely on it)

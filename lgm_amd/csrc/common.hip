@@ -89,7 +89,7 @@ void prof_end(hipStream_t st) {
 
 extern "C" {
 const char *lgm_last_error(void) { return lgm::g_err; }
-int lgm_abi_version(void) { return 10; }
+int lgm_abi_version(void) { return 11; }
 
 lgm_profiler *lgm_profiler_create(void) { return new lgm_profiler(); }
 int lgm_profiler_reset(lgm_profiler *p) {

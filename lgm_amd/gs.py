@@ -304,9 +304,12 @@ class GaussianRenderer:
     def save_mesh(self, gaussians, path, **kw):
         """Additive (the reference's convert.py step): B == 1 as in save_ply; the Gaussians as a closed, coloured triangle
         mesh (lgm_amd.mesh.gaussians_to_mesh, whose keywords `kw` are) written as .obj, or .ply by the path's
-        extension. Returns the Mesh."""
+        extension. fit_iters=K (with texels): the baked texture fitted to renders from this renderer's cameras
+        (lgm_amd.meshraster.fit_texture). Returns the Mesh."""
         from .mesh import gaussians_to_mesh
         assert gaussians.shape[0] == 1, "only support batch size 1"
+        if kw.get("fit_iters"):
+            kw.setdefault("opt", self.opt)
         mesh = gaussians_to_mesh(gaussians, **kw)
         if str(path).lower().endswith(".ply"):
             mesh.save_ply(path)

@@ -6,7 +6,8 @@ nothing is random: two calls on the same input give the same bits.
 
   density_grid       Gaussians [N, 14] -> sigma [Gx, Gy, Gz], rgb [Gx, Gy, Gz, 3]
   extract_surface    sigma (and rgb) -> Mesh
-  gaussians_to_mesh  both, after save_ply's opacity prune (texels=T: bake_texture too)
+  gaussians_to_mesh  both, after save_ply's opacity prune (texels=T: bake_texture too; fit_iters=K: then
+                     lgm_amd.meshraster.fit_texture, K iterations against renders of the Gaussians)
   sample_field       Gaussians, points [..., 3] -> sigma [...], rgb [..., 3]: the same field at arbitrary points
   bake_texture       Mesh, Gaussians -> Mesh with a per-quad UV atlas and the Gaussians' colour at every texel
   Mesh               vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 or None, and optionally
@@ -67,6 +68,7 @@ class Mesh:
     uvs: Optional[torch.Tensor] = None
     face_uvs: Optional[torch.Tensor] = None
     texture: Optional[torch.Tensor] = None
+    fit: Optional[dict] = None  # lgm_amd.meshraster.fit_texture's record: {"loss_first", "loss_last", "iters"}
 
     def _numpy(self):
         v = self.vertices.detach().cpu().numpy().astype(np.float32)
@@ -508,15 +510,27 @@ def bake_texture(mesh: Mesh, gaussians: torch.Tensor, texels: int = 4, bound: fl
 
 def gaussians_to_mesh(gaussians: torch.Tensor, resolution: Union[int, Sequence[int]] = 256, iso: float = 0.5,
                       bound: float = 1.0, min_opacity: float = 0.005, scale_modifier: float = 1.0,
-                      texels: Optional[int] = None) -> Mesh:
+                      texels: Optional[int] = None, fit_iters: int = 0, opt=None, fit_resolution: int = 512,
+                      fit_views: int = 1, fit_lr: float = 0.01, fit_seed: int = 0) -> Mesh:
     """Gaussians [N, 14] or [1, N, 14] -> a closed, coloured triangle mesh: save_ply's opacity prune (>= min_opacity),
     density_grid, extract_surface. resolution = 256 is convert.py's grid; iso = 0.5 is a choice, not a tuned value (no
     trained checkpoint exists offline to tune it on). texels = T: bake_texture of the pruned Gaussians on that mesh,
-    T texels per quad edge (colour detail then no longer depends on the resolution)."""
+    T texels per quad edge (colour detail then no longer depends on the resolution). fit_iters = K > 0 (with texels):
+    that texture then fitted to renders of the pruned Gaussians, lgm_amd.meshraster.fit_texture(iters=K,
+    views=fit_views, resolution=fit_resolution, lr=fit_lr, seed=fit_seed) with the cameras of `opt` (Options() by
+    default); 0: nothing is fitted and nothing changes."""
+    if fit_iters and texels is None:
+        raise ValueError("fit_iters needs texels: the fit is of the baked texture")
     g = _check_gaussians(gaussians)
     g = g[g[:, 3] >= min_opacity]
     sigma, rgb = density_grid(g, resolution, bound, scale_modifier)
     mesh = extract_surface(sigma, rgb, iso, bound)
     if texels is None:
         return mesh
-    return bake_texture(mesh, g, texels, bound, scale_modifier, resolution=resolution)
+    mesh = bake_texture(mesh, g, texels, bound, scale_modifier, resolution=resolution)
+    if not fit_iters:
+        return mesh
+    from .meshraster import fit_texture
+    from .options import Options
+    return fit_texture(mesh, g, Options() if opt is None else opt, iters=int(fit_iters), views=fit_views,
+                       resolution=fit_resolution, lr=fit_lr, seed=fit_seed)

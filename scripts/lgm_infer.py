@@ -6,13 +6,15 @@ and N orbit frames through lgm_amd.cameras.render_orbit_frames. Runs on the GPU 
 
     python scripts/lgm_infer.py [--png tests/golden/catstatue_rgba.png] [--ckpt STATE_DICT.pt] [--frames 8]
                                 [--device cuda|cpu] [--bf16] [--native-conv] [--out bench_out_lgm_infer]
-                                [--mesh] [--mesh-resolution 256] [--mesh-iso 0.5] [--mesh-texels N]
+                                [--mesh [OBJ]] [--mesh-resolution 256] [--mesh-iso 0.5] [--mesh-texels N] [--mesh-fit K]
 
 --native-conv (with --bf16 on the GPU) runs the UNet's stride-1 convolutions on the HIP kernel (UNet.native_conv)
 instead of the library convolution: no first-call solver search.
 --mesh also writes object.obj next to the PLY (lgm_amd.mesh: the Gaussians' density on a grid, surface nets) and adds
 its vertex and face counts to the JSON line. --mesh-texels N bakes a texture from the Gaussians at N texels per quad
-edge (object.mtl and object.png next to the OBJ) and adds its size to the JSON line.
+edge (object.mtl and object.png next to the OBJ) and adds its size to the JSON line. --mesh OBJ writes to that path
+instead. --mesh-fit K (with --mesh-texels) fits that texture to renders of the Gaussians for K iterations
+(lgm_amd.meshraster.fit_texture) and adds the first and last loss to the JSON line.
 """
 from __future__ import annotations
 
@@ -41,11 +43,14 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="run the model under bf16 autocast (GPU)")
     ap.add_argument("--native-conv", action="store_true",
                     help="the UNet's stride-1 convolutions on the HIP kernel (16-bit on the GPU: with --bf16)")
-    ap.add_argument("--mesh", action="store_true", help="also export a coloured triangle mesh (object.obj)")
+    ap.add_argument("--mesh", nargs="?", const=True, default=False, metavar="OBJ",
+                    help="also export a coloured triangle mesh (object.obj in --out, or the given path)")
     ap.add_argument("--mesh-resolution", type=int, default=256)
     ap.add_argument("--mesh-iso", type=float, default=0.5)
     ap.add_argument("--mesh-texels", type=int, default=None,
                     help="with --mesh: texels per quad edge of a texture baked from the Gaussians (default: vertex colours)")
+    ap.add_argument("--mesh-fit", type=int, default=0,
+                    help="with --mesh-texels: iterations of the texture fit against renders of the Gaussians (default: none)")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
@@ -88,13 +93,15 @@ def main():
         mesh_info = {}
         if a.mesh:
             t0 = time.perf_counter()
-            obj = os.path.join(a.out, "object.obj")
+            obj = os.path.join(a.out, "object.obj") if a.mesh is True else a.mesh
             mesh = model.gs.save_mesh(gaussians.float(), obj, resolution=a.mesh_resolution, iso=a.mesh_iso,
-                                      texels=a.mesh_texels)
+                                      texels=a.mesh_texels, fit_iters=a.mesh_fit)
             t["mesh_s"] = time.perf_counter() - t0
             mesh_info = {"mesh": obj, "mesh_vertices": int(mesh.vertices.shape[0]), "mesh_faces": int(mesh.faces.shape[0])}
             if mesh.texture is not None:
                 mesh_info["mesh_texture"] = [int(mesh.texture.shape[1]), int(mesh.texture.shape[0])]  # W, H
+            if mesh.fit is not None:
+                mesh_info["mesh_fit"] = mesh.fit
         t0 = time.perf_counter()
         az = np.arange(a.frames, dtype=np.float64) * (360.0 / max(a.frames, 1))
         frames = render_orbit_frames(model.gs, gaussians, az, radius=opt.cam_radius).cpu().numpy()
