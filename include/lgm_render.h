@@ -167,6 +167,38 @@ size_t lgm_render_workspace_size_opts(int B, int V, int N, int H, int W, long lo
  * it needs lgm_render_count_pairs' pairs_out[1] (upstream's count) as its capacity. Per call, like every option. */
 #define LGM_RENDER_NO_CULL 1
 
+/* LGM_RENDER_ANTIALIAS: opacity compensation of the 0.3 px^2 dilation (the 3DGS rasteriser's `antialiasing` switch,
+ * the Mip-Splatting 2D filter), so a splat smaller than a pixel keeps its integrated alpha instead of covering the
+ * dilated footprint at full opacity. Per (view, Gaussian), with (a0, b, c0) the 2D covariance BEFORE the dilation
+ * (the very sums the dilated a = a0 + 0.3, c = c0 + 0.3 are formed from, never a - 0.3):
+ *   det0 = a0 c0 - b^2,  det = a c - b^2,  r = det0 / det,
+ *   s = sqrt(min(1, fmaxf(2.5e-5, r)))      (fmaxf semantics: a NaN r gives 2.5e-5; r < 1 in exact arithmetic, the
+ *                                            upper clamp only guards fp32 rounding and makes o^ <= o hold),
+ *   o^ = o s  replaces the opacity o wherever it is consumed downstream: the record's L = log2(o^) (so
+ *   lgm_render_records returns that), the o^ <= 1/255 early-out and tau = 2 ln(255 o^) of the exact cull.
+ * Radius, 3-sigma rect, conic and depth do not change. With the bit off, not one operation or operand changes.
+ * s is evaluated in fp64, by a pass of its own ahead of the binning, from the same fp32 inputs and the same sums
+ * (a0 = T0 . Sigma T0, b, c0) and kept as fp32 per (view, Gaussian) in the workspace for the backward: det0 cancels
+ * for an elongated splat (a0 c0 / det0 in the hundreds), and an fp32 evaluation carries that amplification of its
+ * operands' rounding into log2 o^ (1e-5..1e-4). The constants are the rasteriser's fp32 literals (0.3f, 2.5e-5f).
+ * Backward, the exact derivative: with G_v = dL/do^ of view v (what the compositing backward accumulates as the
+ * opacity partial),
+ *   dL/do = sum_v s_v G_v,   dL/ds_v = o G_v,   dL/dr = dL/ds_v / (2 s_v)  where 2.5e-5 < r <= 1, else 0,
+ *   dr/da0 = (c0 det - det0 c) / det^2,  dr/dc0 = (a0 det - det0 a) / det^2,  dr/db = 2 b (det0 - det) / det^2
+ *   (evaluated as 0.3 (c0 c + b^2), 0.3 (a0 a + b^2) and -2 b (0.3 (a0 + c0) + 0.09) over det^2: the same
+ *   numerators with a - a0 = c - c0 = 0.3 put in, free of the cancellation of a large splat's products),
+ * added to the conic's dL/da, dL/db, dL/dc before they are carried to the 3D covariance and the mean.
+ * The opacity partial is then kept per VIEW ([B,V,N], fp32, or int64 fixed point with the per-view flush bound in
+ * deterministic mode) after the other accumulators, followed by the factors s [B,V,N]: the workspace is larger, size
+ * it with
+ * lgm_render_workspace_size_opts(..., options); without the bit the workspace is byte for byte what it was. Pass
+ * the bit to forward and backward alike (the loss-fused pair and packed mode included).
+ * Packed capacity: lgm_render_count_pairs takes no options and counts with the uncompensated opacity. Its
+ * pairs_out[0] remains a valid capacity for an antialiased forward: s <= 1, so o^ <= o, and every step of the cull
+ * (the early-out, tau, the candidate rect, the tile tests) is monotone in the opacity -- the antialiased forward's
+ * own stats_out[0] is at most that count. */
+#define LGM_RENDER_ANTIALIAS 32
+
 #ifdef __cplusplus
 }
 #endif

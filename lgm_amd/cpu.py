@@ -30,7 +30,7 @@ def _tf(M: torch.Tensor, p: torch.Tensor, rows: int) -> torch.Tensor:
 
 
 def _preprocess(g: torch.Tensor, view: torch.Tensor, proj: torch.Tensor, tanx: float, tany: float, H: int, W: int,
-                mod: float):
+                mod: float, antialias: bool = False):
     f32 = torch.float32
     mean = g[:, 0:3]
     hom = _tf(proj, mean, 4)
@@ -65,10 +65,16 @@ def _preprocess(g: torch.Tensor, view: torch.Tensor, proj: torch.Tensor, tanx: f
     T1 = Vw[:, 1][None, :] * J11[:, None] + Vw[:, 2][None, :] * J12[:, None]
     s0 = (Sig @ T0[:, :, None])[:, :, 0]
     s1 = (Sig @ T1[:, :, None])[:, :, 0]
-    a = (T0 * s0).sum(-1) + 0.3
+    a0 = (T0 * s0).sum(-1)
     b = (T0 * s1).sum(-1)
-    c = (T1 * s1).sum(-1) + 0.3
+    c0 = (T1 * s1).sum(-1)
+    a, c = a0 + 0.3, c0 + 0.3
     det = a * c - b * b
+    opacity = g[:, 3]
+    if antialias:  # include/lgm_render.h LGM_RENDER_ANTIALIAS: o sqrt(min(1, fmaxf(2.5e-5, det0 / det)))
+        r = (a0 * c0 - b * b) / det
+        r = torch.where(r > 2.5e-5, r, torch.full_like(r, 2.5e-5))  # (a NaN ratio gives the floor, as fmaxf)
+        opacity = opacity * torch.sqrt(torch.clamp(r, max=1.0))
     mid = 0.5 * (a + c)
     disc = torch.sqrt(torch.clamp(mid * mid - det, min=0.1))
     rad = torch.ceil(3.0 * torch.sqrt(torch.maximum(mid + disc, mid - disc)))
@@ -85,7 +91,7 @@ def _preprocess(g: torch.Tensor, view: torch.Tensor, proj: torch.Tensor, tanx: f
     vis = (depth.detach() > 0.2) & (det.detach() != 0) & ((x1 - x0) * (y1 - y0) > 0)
     inv = 1.0 / torch.where(det == 0, torch.ones_like(det), det)
     conic = torch.stack([c * inv, -b * inv, a * inv], -1)
-    return {"px": px, "py": py, "depth": depth, "conic": conic, "vis": vis, "radii": torch.where(vis, ri, 0),
+    return {"px": px, "py": py, "depth": depth, "conic": conic, "opacity": opacity, "vis": vis, "radii": torch.where(vis, ri, 0),
             "rect": torch.stack([x0, y0, x1, y1], -1), "gx": gx, "gy": gy}
 
 
@@ -131,7 +137,7 @@ def _composite_tile(pre, g, ids, tx, ty, H, W, bg):
         dy = pre["py"][sel][:, None] - pfy[None, :]
         power = -0.5 * (con[:, 0:1] * dx * dx + con[:, 2:3] * dy * dy) - con[:, 1:2] * dx * dy
         # min(0.99, o G) with upstream's backward, which differentiates o G even where the cap is active
-        og = g[sel, 3][:, None] * torch.exp(power)
+        og = pre["opacity"][sel][:, None] * torch.exp(power)
         alpha = og + (torch.clamp(og, max=0.99) - og).detach()
         valid = (power <= 0) & (alpha >= 1.0 / 255.0)
         a_eff = torch.where(valid, alpha, torch.zeros_like(alpha))
@@ -155,9 +161,11 @@ def _composite_tile(pre, g, ids, tx, ty, H, W, bg):
     return C, D, T, pid
 
 
-def render_cpu(gaussians, cam_view, cam_view_proj, bg, tanx, tany, H, W, scale_modifier=1.0, clamp=False):
+def render_cpu(gaussians, cam_view, cam_view_proj, bg, tanx, tany, H, W, scale_modifier=1.0, clamp=False,
+               antialias=False):
     """[B,N,14] CPU Gaussians -> (image [B,V,3,H,W], depth [B,V,1,H,W], alpha [B,V,1,H,W]); image clamped to
-    [0, 1] when clamp (core/gs.py:87)."""
+    [0, 1] when clamp (core/gs.py:87). antialias: the opacity compensation of LGM_RENDER_ANTIALIAS
+    (include/lgm_render.h), differentiated by autograd like the rest."""
     g_all = gaussians.float()
     B, V = cam_view.shape[0], cam_view.shape[1]
     bgv = torch.as_tensor(bg, dtype=torch.float32).reshape(3)
@@ -166,7 +174,7 @@ def render_cpu(gaussians, cam_view, cam_view_proj, bg, tanx, tany, H, W, scale_m
         g = g_all[b]
         for v in range(V):
             pre = _preprocess(g, cam_view[b, v].float(), cam_view_proj[b, v].float(), tanx, tany, H, W,
-                              float(scale_modifier))
+                              float(scale_modifier), antialias)
             start, lst = _tile_lists(pre)
             color = torch.zeros(3, H * W)
             depth = torch.zeros(H * W)

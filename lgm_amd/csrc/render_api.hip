@@ -39,6 +39,7 @@ int check_common(int B, int V, int N, int H, int W, const void *g, const void *c
     d.gt_img = d.gt_mask = nullptr;
     d.loss_part = d.loss_out = nullptr;
     d.d_loss = nullptr;
+    d.aa_s = nullptr;
     return LGM_OK;
 }
 
@@ -101,7 +102,8 @@ size_t lgm_render_workspace_size(int B, int V, int N, int H, int W, long long pa
 
 size_t lgm_render_workspace_size_opts(int B, int V, int N, int H, int W, long long pair_capacity, int options) {
     if (B <= 0 || V <= 0 || N < 0 || H <= 0 || W <= 0) return 0;
-    return lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0).total;
+    return lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0,
+                                               (options & LGM_RENDER_ANTIALIAS) != 0).total;
 }
 
 int lgm_render_count_pairs(int B, int V, int N, int H, int W, const float *gaussians, const float *cam_view,
@@ -143,7 +145,8 @@ static int forward_impl(int B, int V, int N, int H, int W, const float *gaussian
         lgm::set_error("null output pointer");
         return LGM_E_INVALID;
     }
-    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0);
+    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0,
+                                               (options & LGM_RENDER_ANTIALIAS) != 0);
     if (!L.slot && !capacity_ok(L.cap)) {  // packed tile offsets are int32; slot offsets are 64-bit
         lgm::set_error("pair capacity %lld exceeds 2^31", L.cap);
         return LGM_E_INVALID;
@@ -154,6 +157,8 @@ static int forward_impl(int B, int V, int N, int H, int W, const float *gaussian
     }
     char *ws = (char *)workspace;
     d.options = options & ~LGM_RENDER_FUSED_LOSS;
+    if (options & LGM_RENDER_ANTIALIAS)
+        d.aa_s = lgm::acc_aa_factors((const char *)workspace + L.accum, B, V, N, (options & LGM_RENDER_DETERMINISTIC) != 0);
     if (gt_images || gt_masks || loss_out) {
         if (!gt_images || !gt_masks || !loss_out) {
             lgm::set_error("fused loss needs gt_images, gt_masks and loss_out");
@@ -188,13 +193,16 @@ static int backward_impl(int B, int V, int N, int H, int W, const float *gaussia
         lgm::set_error("null pointer in backward");
         return LGM_E_INVALID;
     }
-    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0);
+    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0,
+                                               (options & LGM_RENDER_ANTIALIAS) != 0);
     if (!workspace || workspace_bytes < L.total) {
         lgm::set_error("workspace too small (%zu < %zu)", workspace_bytes, L.total);
         return LGM_E_WORKSPACE;
     }
     if (N == 0) return LGM_OK;
     d.options = options & ~LGM_RENDER_FUSED_LOSS;
+    if (options & LGM_RENDER_ANTIALIAS)
+        d.aa_s = lgm::acc_aa_factors((const char *)workspace + L.accum, B, V, N, (options & LGM_RENDER_DETERMINISTIC) != 0);
     if (gt_images || gt_masks || d_loss) {
         if (!gt_images || !gt_masks || !d_loss) {
             lgm::set_error("fused loss backward needs gt_images, gt_masks and d_loss");

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin
         const float2 *gp = reinterpret_cast<const float2 *>(gauss + ((size_t)b * d.N + i) * 14);
         const float2 g01 = gp[0], g23 = gp[1];
         const float gm[4] = {g01.x, g01.y, g23.x, g23.y};
-        vis = preprocess_view(gm, c3, views + 16 * bv, projs + 16 * bv, d, o);
+        vis = preprocess_view(gm, c3, views + 16 * bv, projs + 16 * bv, d, o, d.aa_s + (size_t)bv * d.N, i);
         if (MODE != COUNT) {
             const size_t k = (size_t)bv * d.N + i;
             if (vis) {
@@ -375,6 +375,52 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin
         atomicAdd(&misc[1], s_tot[1]);
     }
     if (corder && blockIdx.x == 0 && blockIdx.y == 0) center_order(d.gx, T, corder, hist);
+}
+
+// k_aa_factor (LGM_RENDER_ANTIALIAS only): grid (ceil(N / 256), B * V), block 256. The opacity factor
+//   s = sqrt(min(1, fmax(2.5e-5, det0 / det))),  det0 = a0 c0 - b^2,  det = (a0 + 0.3)(c0 + 0.3) - b^2   (lgm_render.h)
+// of every (view, Gaussian), written as fp32 to the workspace (acc_aa_factors) ahead of the binning; preprocess_view
+// and k_preproc_bwd read it. It restates cov2d's sums -- the 1.3 tan-fov clamp, T = W J, Sigma = M^T M, a0 = T0 . Sigma
+// T0, b, c0 -- in fp64 on the same fp32 inputs (and upstream's fp32 literals: 0.3f, 1.3f tan), because det0 cancels:
+// for an elongated splat a0 c0 / det0 reaches hundreds, and the fp32 rounding a0, b and c0 carry is amplified by it
+// in r (measured: log2 o^ up to 1e-4 from the exact value in any fp32 evaluation, 6e-7 with this pass). A pass of
+// its own, so k_bin's registers are as without the option; one thread per (view, Gaussian), no shared state.
+__global__ __launch_bounds__(256) void k_aa_factor(Dims d, const float *__restrict__ gauss,
+                                                   const float *__restrict__ views, float *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x, bv = blockIdx.y;
+    if (i >= d.N) return;
+    const float *g = gauss + ((size_t)(bv / d.V) * d.N + i) * 14, *Vw = views + 16 * bv;
+    const double mx = g[0], my = g[1], mz = g[2];
+    double t[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = Vw[k] * mx + Vw[4 + k] * my + Vw[8 + k] * mz + Vw[12 + k];
+    const double limx = (double)(1.3f * d.tanx), limy = (double)(1.3f * d.tany), tz = t[2];
+    const double tx = fmin(limx, fmax(-limx, t[0] / tz)) * tz, ty = fmin(limy, fmax(-limy, t[1] / tz)) * tz;
+    const double J00 = d.fx / tz, J02 = -(d.fx * tx) / (tz * tz), J11 = d.fy / tz, J12 = -(d.fy * ty) / (tz * tz);
+    double T0[3], T1[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        T0[r] = Vw[4 * r + 0] * J00 + Vw[4 * r + 2] * J02;
+        T1[r] = Vw[4 * r + 1] * J11 + Vw[4 * r + 2] * J12;
+    }
+    const double qr = g[7], x = g[8], y = g[9], z = g[10];  // un-normalised quaternion (quat_rot)
+    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - qr * z), 2.0 * (x * z + qr * y)},
+                            {2.0 * (x * y + qr * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - qr * x)},
+                            {2.0 * (x * z - qr * y), 2.0 * (y * z + qr * x), 1.0 - 2.0 * (x * x + y * y)}};
+    // u = M^T T0, v = M^T T1 with M[c][k] = s_k R[c][k] (cov3d): a0 = u . u, b = u . v, c0 = v . v
+    double a0 = 0.0, b = 0.0, c0 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double sk = (double)d.mod * g[4 + k];
+        const double u = sk * (R[0][k] * T0[0] + R[1][k] * T0[1] + R[2][k] * T0[2]);
+        const double v = sk * (R[0][k] * T1[0] + R[1][k] * T1[1] + R[2][k] * T1[2]);
+        a0 += u * u;
+        b += u * v;
+        c0 += v * v;
+    }
+    const double dil = (double)0.3f;
+    const double r = (a0 * c0 - b * b) / ((a0 + dil) * (c0 + dil) - b * b);
+    out[(size_t)bv * d.N + i] = (float)sqrt(fmin(1.0, fmax((double)AA_RMIN, r)));  // (fmax drops a NaN ratio)
 }
 
 // The k_bin instantiation of a launch (launch_binning).
@@ -891,7 +937,27 @@ int launch_binning(const Dims &d, const float *gaussians, const float *cam_view,
     int *tcount = (int *)(ws + L.tile_count), *tstart = (int *)(ws + L.tile_start);
     unsigned long long *pairs = (unsigned long long *)(ws + L.pairs), *misc = (unsigned long long *)(ws + L.misc);
     float *accum = (float *)(ws + L.accum);
-    const size_t lds = d.T <= LDS_HIST_MAX ? 3 * (size_t)d.T * 4 : 0;
+    // LGM_RENDER_ANTIALIAS: the per-view opacity partials (acc_aa_offset) start at zero; the other accumulators are
+    // zeroed by k_render_fwd's epilogue and, the fp64 side block, by k_bin
+    // and the factors themselves are written ahead of the count pass and the binning (k_aa_factor). (The count-only
+    // pass of lgm_render_count_pairs takes no options; its workspace has no such block.)
+    if (count_only && (d.options & LGM_RENDER_ANTIALIAS)) {
+        set_error("the counting pass takes no LGM_RENDER_ANTIALIAS");
+        return LGM_E_INVALID;
+    }
+    if ((d.options & LGM_RENDER_ANTIALIAS) && d.N > 0) {
+        const bool det = (d.options & LGM_RENDER_DETERMINISTIC) != 0;
+        if (hipMemsetAsync(ws + L.accum + acc_clear_bytes(d.B, d.V, d.N, det, false), 0,
+                           acc_clear_bytes(d.B, d.V, d.N, det, true) - acc_clear_bytes(d.B, d.V, d.N, det, false),
+                           st) != hipSuccess) {
+            set_error("hipMemsetAsync failed");
+            return LGM_E_HIP;
+        }
+        LGM_LAUNCH("k_aa_factor", st, (k_aa_factor<<<dim3((d.N + 255) / 256, d.BV), 256, 0, st>>>(
+                                          d, gaussians, cam_view,
+                                          const_cast<float *>(d.aa_s))));
+    }
+    const size_t lds =d.T <= LDS_HIST_MAX ? 3 * (size_t)d.T * 4 : 0;
     // k_sort's centre-first tile table (the first T ints of the order buffer; the binning histogram's 3T ints of LDS
     // hold its counting sort)
     int *corder = lds && d.T >= 8 ? (int *)(ws + L.order) : nullptr;

@@ -31,6 +31,26 @@ __host__ __device__ inline size_t acc_elems(size_t B, size_t V, size_t N) { retu
 // stored record (rec_needle) identically by the binning, the backward's flush and the preprocess backward (via a
 // flag in bit 31 of the record's rect).
 __host__ __device__ inline size_t acc_side_offset(size_t B, size_t V, size_t N) { return (acc_elems(B, V, N) + 1) & ~(size_t)1; }
+// LGM_RENDER_ANTIALIAS: the opacity partial per (view, Gaussian) instead of per scene (the preprocess backward needs
+// dL/do^ of each view: lgm_render.h), one element (fp32, or int64 in deterministic mode) per (view, Gaussian), placed
+// after everything above -- the fp64 side block in float mode -- and then the factors s themselves, one fp32 per
+// (view, Gaussian) (k_aa_factor writes them ahead of the binning; the binning and the preprocess backward read them).
+// Both are present only with the bit. acc_aa_offset: the partials' offset in elements; acc_clear_bytes: the bytes a
+// repeated backward clears (every accumulator, the partials included, not the factors); acc_bytes: the whole block.
+__host__ __device__ inline size_t acc_aa_offset(size_t B, size_t V, size_t N, bool det) {
+    return det ? acc_elems(B, V, N) : acc_side_offset(B, V, N) + B * V * N * 6;
+}
+__host__ __device__ inline size_t acc_clear_bytes(size_t B, size_t V, size_t N, bool det, bool aa) {
+    return (det ? acc_elems(B, V, N) * 8 : acc_side_offset(B, V, N) * 4 + B * V * N * 3 * 8) +
+           (aa ? B * V * N * (det ? 8 : 4) : 0);
+}
+__host__ __device__ inline size_t acc_bytes(size_t B, size_t V, size_t N, bool det, bool aa) {
+    return acc_clear_bytes(B, V, N, det, aa) + (aa ? B * V * N * 4 : 0);
+}
+// the factors of a call with the bit (accum: the accumulator block's start)
+__host__ __device__ __forceinline__ const float *acc_aa_factors(const void *accum, size_t B, size_t V, size_t N, bool det) {
+    return reinterpret_cast<const float *>(static_cast<const char *>(accum) + acc_clear_bytes(B, V, N, det, true));
+}
 // Deterministic mode's per-flush overflow bound (k_render_bwd): in that mode an accumulator takes at most one flush
 // per tile list its Gaussian appears in -- one work item per tile, an entry once per list. A per-view record (mean2D,
 // conic, depth) sees the T tiles of its view; a per-scene record (opacity, colour: acc_index q = 5..8) the V * T
@@ -90,7 +110,8 @@ __host__ __device__ __forceinline__ int ck_shift_for(size_t) { return 0; }
 __host__ __device__ __forceinline__ int ck_shift_for(size_t tiles) { return tiles >= CK_LONG_TILES ? 1 : 0; }
 #endif
 
-inline Layout make_layout(int B, int V, int N, int H, int W, long long pair_capacity, bool det = false) {
+inline Layout make_layout(int B, int V, int N, int H, int W, long long pair_capacity, bool det = false,
+                          bool aa = false) {
     const size_t BV = (size_t)B * V, T = (size_t)((W + BX - 1) / BX) * ((H + BY - 1) / BY), P = (size_t)H * W;
     Layout L;
     L.slot = pair_capacity <= 0;
@@ -124,7 +145,7 @@ inline Layout make_layout(int B, int V, int N, int H, int W, long long pair_capa
     L.cklist = take((size_t)L.ck_slots * 8);
     L.nck = take(BV * T * 4);
     L.cmask = take(BV * P);
-    L.accum = take(det ? acc_elems(B, V, N) * 8 : acc_side_offset(B, V, N) * 4 + BV * N * 3 * 8);
+    L.accum = take(acc_bytes(B, V, N, det, aa));  // (aa: + the per-view opacity partials, acc_aa_offset)
     L.lossp = take(BV * T * 2 * 4);  // per-tile sums of squared image / alpha residuals (fused loss)
     L.lossw = take(((BV * T + 2047) / 2048) * 16);  // their per-workgroup double2 partials (k_loss_reduce)
     L.detmax = take(64 * 4);  // deterministic mode: max |dL/dpixel| over the seeds, in 64 atomicMax slots
@@ -137,7 +158,8 @@ struct Dims {
     float tanx, tany, fx, fy, mod;
     unsigned long long *counters;  // this call's device work counters (lgm_diag.render_counters), or null
     int det_lim_log2;              // lgm_diag.det_limit_log2 (test hook; 0 = the derived bound)
-    int options;                   // per-call LGM_RENDER_* bits (NO_CULL, CLAMP_IMAGE, FUSED_LOSS, DETERMINISTIC)
+    int options;                   // per-call LGM_RENDER_* bits (NO_CULL, CLAMP_IMAGE, FUSED_LOSS, DETERMINISTIC,
+                                   // ANTIALIAS)
     int ck_shift;                  // backward work items span 2^ck_shift forward chunks (ck_shift_for(BV * T))
     // LGM_RENDER_FUSED_LOSS (core/models.py:138-160): ground truth [BV,3,P] / [BV,P], the per-tile loss partials
     // (forward) and the gradients of the two MSE terms (backward)
@@ -145,6 +167,9 @@ struct Dims {
     float *loss_part;  // workspace: per-tile (image, alpha) sums of squared residuals
     float *loss_out;   // DEVICE float[4]: loss_mse, mse_image, mse_alpha, psnr
     const float *d_loss;  // DEVICE float[2]: dL/dmse_image, dL/dmse_alpha
+    // LGM_RENDER_ANTIALIAS: the workspace's opacity factors s [BV, N] (acc_aa_factors; k_aa_factor writes them ahead
+    // of the binning), else null
+    const float *aa_s;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -234,6 +259,7 @@ __device__ __forceinline__ void cov2d(const ProjCtx &P, const float c3[6], float
     b = s1[0] * P.T0[0] + s1[1] * P.T0[1] + s1[2] * P.T0[2];
     c = P.T1[0] * s1[0] + P.T1[1] * s1[1] + P.T1[2] * s1[2] + 0.3f;
 }
+constexpr float AA_RMIN = 2.5e-5f;  // LGM_RENDER_ANTIALIAS: the floor of det0 / det (lgm_render.h)
 
 __device__ __forceinline__ float ndc2pix(float v, int S) { return (float)((((double)v + 1.0) * S - 1.0) * 0.5); }
 
@@ -333,7 +359,7 @@ __device__ __forceinline__ void gaussian_cov3d(const float *g, float mod, float 
     cov3d(s, R, c3);
 }
 __device__ __forceinline__ bool preprocess_view(const float *g, const float c3[6], const float *Vw, const float *Pm,
-                                                const Dims &d, Geo &o) {
+                                                const Dims &d, Geo &o, const float *aa_row, int i) {
 #pragma clang fp contract(off)
     float hom[4], pv[3];
     xf44(Pm, g[0], g[1], g[2], hom);
@@ -360,10 +386,21 @@ __device__ __forceinline__ bool preprocess_view(const float *g, const float c3[6
     if ((x1 - x0) * (y1 - y0) == 0) return false;
     o.x = px; o.y = py; o.depth = pv[2];
     o.A = c * det_inv; o.B = -b * det_inv; o.C = a * det_inv;
-    o.opacity = g[3];
+    // the opacity every later step consumes: o, or o^ = o s with LGM_RENDER_ANTIALIAS (a runtime branch: k_bin's
+    // instantiations and their register budget stay as they are). s of Gaussian i in this view (aa_row: the view's
+    // row of Dims::aa_s) was written by k_aa_factor: det0 = a0 c0 - b^2 cancels for an elongated splat -- a0 c0 / det0
+    // reaches hundreds -- and in fp32 that amplification of the operands' rounding is in log2 o^ (1e-5..1e-4)
+    float op = g[3];
+    if (d.options & LGM_RENDER_ANTIALIAS) {
+        // (the index tied to the rect just computed: a load hoisted to the top of the preprocess would hold a register
+        // across it, and k_bin has none to spare)
+        int ii = i;
+        asm volatile("" : "+v"(ii) : "v"(y1));
+        op *= aa_row[ii];
+    }
+    o.opacity = op;
     o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1; o.radius = r;
     // --- exact opacity-aware cull of the emitted rect
-    const float op = g[3];
     if (d.options & LGM_RENDER_NO_CULL) {
         o.hx = o.hy = 3.0e38f;
         o.tau = 3.0e38f;

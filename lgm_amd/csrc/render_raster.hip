@@ -614,6 +614,11 @@ __device__ __forceinline__ DetNorm det_norm(float Ap, float Bp, float Cp, int W,
     n.k[5] = 0;
     return n;
 }
+// LGM_RENDER_ANTIALIAS's per-view opacity partial dL/do^ = (sum_p w) / o^: normalised by o^'s own power of two, from
+// the record's L = log2(o^) (<= 0; so k_render_bwd and k_preproc_bwd derive bitwise the same exponent): the
+// normalised flush is the plain pixel sum of w = G dL/dG, bounded like the other per-view partials, however small
+// the compensated opacity of a sub-pixel splat is.
+__device__ __forceinline__ int det_norm_opacity(float L) { return (int)fminf(0.f, fmaxf(-60.f, floorf(L))); }
 
 // k_det_seed_max: grid (min(B*V*T, DET_MAX_WGS)), block 256, each workgroup striding over tiles: max |dL/dpixel|
 // over every seed of the call -> det_max[DET_SLOTS] (float bits, atomicMax on the non-negative bit pattern, slot
@@ -678,7 +683,9 @@ __global__ __launch_bounds__(256) void k_det_seed_max(Dims d, const float *__res
 // entry and flushed once per (chunk, entry) to the per-view accumulators.
 // Occupancy: at least 4 waves per SIMD for the register allocation (<= 128 VGPRs; the 64-entry chunks' LDS admits 4
 // workgroups per CU); 2 for the depth-gradient instantiation, which LGM never runs.
-template <bool DEPTH, bool LOSS, bool DET>  // DET: LGM_RENDER_DETERMINISTIC (int64 fixed-point flush)
+// AA: LGM_RENDER_ANTIALIAS -- the opacity partial is flushed per (view, Gaussian) (acc_aa_offset) instead of into the
+// scene's record: k_preproc_bwd needs dL/do^ of each view. Compile-time, so the other instantiations are unchanged.
+template <bool DEPTH, bool LOSS, bool DET, bool AA = false>  // DET: LGM_RENDER_DETERMINISTIC (int64 fixed-point flush)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 : 4))) void k_render_bwd(
     Dims d, long long slot_stride, const int *__restrict__ tile_start,
     const int *__restrict__ tile_count, const unsigned long long *__restrict__ pairs, const float4 *__restrict__ gP,
@@ -1097,7 +1104,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
                     if (DET) {
                         p0 = ldexpf(p0, det_s + nm.k[0]);
                         p1 = ldexpf(p1, det_s + nm.k[1]);
-                        p5 = ldexpf(p5, det_s);
+                        p5 = ldexpf(p5, det_s + (AA ? det_norm_opacity(Qj.y) : 0));
                     }
                     o[0 * LS + j] = p0;
                     o[1 * LS + j] = p1;
@@ -1152,14 +1159,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
             if (q < NV && j < CH && b0 + j < s1) {
                 const float a = o[q * LS + j];
                 const unsigned gid = sId[j];
-                const size_t ai = acc_index(q, gbase + gid, (size_t)b * d.N + gid, (size_t)d.BV * d.N);
+                size_t ai = acc_index(q, gbase + gid, (size_t)b * d.N + gid, (size_t)d.BV * d.N);
+                if (AA && q == 5) ai = acc_aa_offset(d.B, d.V, d.N, DET) + gbase + gid;  // per view, not per scene
                 if (a != 0.f) {
                     if (DET) {  // integer adds commute: order-independent sums (a is already in fixed-point units)
                         // (a per-view record takes at most T flushes, a per-scene one (q = 5..8) V * T: with |a|
                         // below the record's bound no sum reaches 2^62 whatever the flushes' signs; the design value
                         // is |a| <= ~2^51 per flush. A flush beyond the bound is counted and k_preproc_bwd then
                         // poisons the call's gradients with NaN instead of returning possibly wrapped sums)
-                        if (!(fabsf(a) <= (q >= 5 && q < 9 ? det_lim_s : det_lim_v))) atomicAdd(det_sat, 1u);
+                        if (!(fabsf(a) <= (q >= 5 + (AA ? 1 : 0) && q < 9 ? det_lim_s : det_lim_v))) atomicAdd(det_sat, 1u);
                         atomicAdd(reinterpret_cast<unsigned long long *>(accum) + ai,
                                   (unsigned long long)__float2ll_rn(fminf(fmaxf(a, -9.0e18f), 9.0e18f)));
                     } else {
@@ -1230,7 +1238,8 @@ __device__ __forceinline__ ProjCtx make_proj_bwd(const float *Vw, float mx, floa
     }
     return P;
 }
-__device__ __forceinline__ void cov2d_bwd(const ProjCtx &P, const float c3[6], float &a, float &b, float &c) {
+__device__ __forceinline__ void cov2d_bwd(const ProjCtx &P, const float c3[6], float &a, float &b, float &c, float &a0,
+                                          float &c0) {  // (a0, c0: before the dilation, for LGM_RENDER_ANTIALIAS)
     const float S[3][3] = {{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}};
     float s0[3], s1[3];
 #pragma unroll
@@ -1238,9 +1247,11 @@ __device__ __forceinline__ void cov2d_bwd(const ProjCtx &P, const float c3[6], f
         s0[k] = S[k][0] * P.T0[0] + S[k][1] * P.T0[1] + S[k][2] * P.T0[2];
         s1[k] = S[k][0] * P.T1[0] + S[k][1] * P.T1[1] + S[k][2] * P.T1[2];
     }
-    a = P.T0[0] * s0[0] + P.T0[1] * s0[1] + P.T0[2] * s0[2] + 0.3f;
+    a0 = P.T0[0] * s0[0] + P.T0[1] * s0[1] + P.T0[2] * s0[2];
     b = s1[0] * P.T0[0] + s1[1] * P.T0[1] + s1[2] * P.T0[2];
-    c = P.T1[0] * s1[0] + P.T1[1] * s1[1] + P.T1[2] * s1[2] + 0.3f;
+    c0 = P.T1[0] * s1[0] + P.T1[1] * s1[1] + P.T1[2] * s1[2];
+    a = a0 + 0.3f;
+    c = c0 + 0.3f;
 }
 
 // k_preproc_bwd: grid (ceil(N/256), B), block 256. Sums over the scene's views in order (deterministic; the
@@ -1251,7 +1262,9 @@ __device__ __forceinline__ void cov2d_bwd(const ProjCtx &P, const float c3[6], f
 // scalar-load round trips for the matrices, in series: pool 57.4 -> 52.3 us, one scene 16.5 -> 14.2 us, outputs
 // bitwise equal (profiles/r05/ab_preproc_lds).
 constexpr int PRE_MAXV = 32;
-template <bool LDSV>
+// AA: LGM_RENDER_ANTIALIAS compiled in (the opacity partial per view, the factor s_v and its derivative: lgm_render.h);
+// compile-time, so the plain instantiations keep their registers (as a runtime branch: 91 -> 104 and 106 -> 119 VGPRs).
+template <bool LDSV, bool AA = false>
 __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__restrict__ gauss,
                                                      const float *__restrict__ views,
                                                      const float *__restrict__ projs, const uint2 *__restrict__ rects,
@@ -1263,6 +1276,9 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
     const bool det = (d.options & LGM_RENDER_DETERMINISTIC) != 0;
     const int det_s = det ? det_seed_shift(det_max) : 0;
     const bool det_bad = det && *det_sat != 0u;  // a fixed-point flush overflowed (k_render_bwd): poison the call
+    // LGM_RENDER_ANTIALIAS: the opacity partial arrives per view (G_v = dL/do^, acc_aa_offset), not per scene
+    constexpr bool aa = AA;
+    const size_t aa_off = aa ? acc_aa_offset(d.B, d.V, d.N, det) : 0;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     // diagnostics: workgroup g's start / end in slots [2], [3] of per-tile record g (unused by the other kernels)
@@ -1276,6 +1292,7 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
     // rect and row are loaded while view v is processed
     uint2 r_nx = make_uint2(0u, 0u);
     float2 acc_nx[NACC_V / 2];
+    float aa_nx = 0.f, aa_snx = 0.f;  // (antialias) the view's opacity partial (float mode) and factor s_v
     auto load_view = [&](int v) {
         const size_t k = ((size_t)b * d.V + v) * d.N + i;
         r_nx = rects[k];
@@ -1283,7 +1300,9 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
             const float2 *acc2 = reinterpret_cast<const float2 *>(accum + k * NACC_V);
 #pragma unroll
             for (int q = 0; q < NACC_V / 2; q++) acc_nx[q] = acc2[q];
+            if (aa) aa_nx = accum[aa_off + k];
         }
+        if (aa) aa_snx = d.aa_s[k];  // (k_aa_factor: the forward's own s_v)
     };
     float g[14];
     const size_t ks = (size_t)d.BV * d.N * NACC_V + ((size_t)b * d.N + i) * NACC_S;  // view-independent partials
@@ -1321,6 +1340,7 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
         float2 acc_e[NACC_V / 2];
 #pragma unroll
         for (int q = 0; q < NACC_V / 2; q++) acc_e[q] = acc_nx[q];
+        const float aa_e = aa_nx, sv = aa_snx;
         if (LDSV && v + 1 < d.V) load_view(v + 1);
         const bool vis = (r.x & 0xffff) != (r.y & 0xffff);
         if (!vis) {
@@ -1359,15 +1379,40 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
         const float *Pm = LDSV ? s_vp[v] + 16 : projs + 16 * bv;
         // ---- cov2D backward
         const ProjCtx Pc = make_proj_bwd(Vw, g[0], g[1], g[2], fx, fy, d.tanx, d.tany);
-        float a, bb, c;
-        cov2d_bwd(Pc, c3, a, bb, c);
+        float a, bb, c, a0, c0;
+        cov2d_bwd(Pc, c3, a, bb, c, a0, c0);
         const float denom = a * c - bb * bb;
         const float denom2inv = __builtin_amdgcn_rcpf((denom * denom) + 0.0000001f);
+        float aa_da = 0, aa_db = 0, aa_dc = 0;
+        if (aa) {  // o^ = o s_v, s_v = sqrt(clamp(det0 / det)) (lgm_render.h): dL/do, and dL/ds_v -> a0, b, c0
+            float Gv = aa_e;  // dL/do^ of this view
+            if (det)
+                Gv = (float)ldexp((double)(reinterpret_cast<const long long *>(accum) + aa_off)[k],
+                                  -(det_s + det_norm_opacity(gQ[k].y)));
+            // s_v is the forward's (fp64-evaluated) factor: at the floor 0.005 or at 1 it is a constant
+            const float rdet = __builtin_amdgcn_rcpf(denom);
+            const bool open = sv * sv > AA_RMIN && sv < 1.0f;
+            dop += sv * Gv;
+            if (open) {
+                // dL/dr / det^2, and det^2 dr/d(a0, b, c0) with a - a0 = c - c0 = 0.3 put in: (c0 det - det0 c) =
+                // 0.3 (c0 c + b^2), (a0 det - det0 a) = 0.3 (a0 a + b^2), det0 - det = -(0.3 (a0 + c0) + 0.09) --
+                // the same derivative without the differences of products that cancel for a large splat
+                const float dr = 0.5f * g[3] * Gv * __builtin_amdgcn_rcpf(sv) * rdet * rdet;
+                aa_da = dr * 0.3f * (c0 * c + bb * bb);
+                aa_dc = dr * 0.3f * (a0 * a + bb * bb);
+                aa_db = -dr * 2 * bb * (0.3f * (a0 + c0) + 0.09f);
+            }
+        }
         float dL_da = 0, dL_db = 0, dL_dc = 0;
         if (denom2inv != 0) {
             dL_da = denom2inv * (-c * c * dcx + 2 * bb * c * dcy + (denom - a * c) * dcz);
             dL_dc = denom2inv * (-a * a * dcz + 2 * a * bb * dcy + (denom - a * c) * dcx);
             dL_db = denom2inv * 2 * (bb * c * dcx - (denom + 2 * bb * bb) * dcy + a * bb * dcz);
+            if (aa) {  // the opacity factor's share (not added at all without the bit: x + 0 may change a zero's sign)
+                dL_da += aa_da;
+                dL_db += aa_db;
+                dL_dc += aa_dc;
+            }
             const float *t0 = Pc.T0, *t1 = Pc.T1;
             dcov[0] += (t0[0] * t0[0] * dL_da + t0[0] * t1[0] * dL_db + t1[0] * t1[0] * dL_dc);
             dcov[3] += (t0[1] * t0[1] * dL_da + t0[1] * t1[1] * dL_db + t1[1] * t1[1] * dL_dc);
@@ -1415,12 +1460,12 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
     {  // the scene's view-independent partials (opacity, colour), summed over its views by the backward's atomics
         if (det) {
             const long long *a = reinterpret_cast<const long long *>(accum) + ks;
-            dop = (float)ldexp((double)a[0], -det_s);
+            if (!aa) dop = (float)ldexp((double)a[0], -det_s);
 #pragma unroll
             for (int q = 0; q < 3; q++) dcol[q] = (float)ldexp((double)a[1 + q], -det_s);
         } else {
             const float4 a = LDSV ? acc_s : *reinterpret_cast<const float4 *>(accum + ks);
-            dop = a.x;
+            if (!aa) dop = a.x;
             dcol[0] = a.y; dcol[1] = a.z; dcol[2] = a.w;
         }
     }
@@ -1498,10 +1543,10 @@ int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_vi
                       float *d_gaussians, float *d_means2D, char *ws, const Layout &L, hipStream_t st) {
     // the accumulators were zeroed by the forward (k_render_fwd's epilogue); a repeated backward of the same forward
     // clears what the previous one left
+    // (with LGM_RENDER_ANTIALIAS the per-view opacity partials, which end the block, included)
     if ((d.options & LGM_RENDER_BACKWARD_AGAIN) &&
-        hipMemsetAsync(ws + L.accum, 0, (d.options & LGM_RENDER_DETERMINISTIC)
-                                            ? acc_elems(d.B, d.V, d.N) * 8
-                                            : acc_side_offset(d.B, d.V, d.N) * 4 + (size_t)d.BV * d.N * 24,
+        hipMemsetAsync(ws + L.accum, 0, acc_clear_bytes(d.B, d.V, d.N, (d.options & LGM_RENDER_DETERMINISTIC) != 0,
+                                                        (d.options & LGM_RENDER_ANTIALIAS) != 0),
                        st) != hipSuccess) {
         set_error("hipMemsetAsync failed");
         return LGM_E_HIP;
@@ -1520,8 +1565,12 @@ int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_vi
                                              d_image, d_depth, d_alpha, (const unsigned char *)(ws + L.cmask),
                                              det_max, (unsigned *)(ws + L.misc) + 13)));
     }
+    const bool aa = (d.options & LGM_RENDER_ANTIALIAS) != 0;
     auto pick = [&](auto depth_tag) {
         constexpr bool DP = decltype(depth_tag)::value;
+        if (aa)
+            return loss ? (det ? k_render_bwd<DP, true, true, true> : k_render_bwd<DP, true, false, true>)
+                        : (det ? k_render_bwd<DP, false, true, true> : k_render_bwd<DP, false, false, true>);
         return loss ? (det ? k_render_bwd<DP, true, true> : k_render_bwd<DP, true, false>)
                     : (det ? k_render_bwd<DP, false, true> : k_render_bwd<DP, false, false>);
     };
@@ -1541,7 +1590,8 @@ int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_vi
                                        // (debug counters: after the per-tile and per-binning-workgroup records)
                                        8 + 8LL * d.BV * d.T + 8LL * d.BV * ((d.N + 511) / 512))));
     dim3 grid((d.N + 255) / 256, d.B);
-    auto pre = d.V <= PRE_MAXV ? k_preproc_bwd<true> : k_preproc_bwd<false>;
+    auto pre = aa ? (d.V <= PRE_MAXV ? k_preproc_bwd<true, true> : k_preproc_bwd<false, true>)
+                  : (d.V <= PRE_MAXV ? k_preproc_bwd<true> : k_preproc_bwd<false>);
     LGM_LAUNCH("k_preproc_bwd", st, (pre<<<grid, 256, 0, st>>>(d, gaussians, cam_view, cam_view_proj,
                                                                         (const uint2 *)(ws + L.rects),
                                                                         (float *)(ws + L.accum), d_gaussians,

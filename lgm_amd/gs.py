@@ -70,7 +70,10 @@ class _RasterizeBatched(torch.autograd.Function):
         if not _slot_fits(ws_bytes, dev):
             # exact pair count (the reference syncs once per view for this; we sync once per batch)
             k = _count_pairs(g, cam_view, cam_view_proj, tanx, tany, scale_modifier, H, W)
-            # pairs actually binned (upstream's full count with LGM_RENDER_NO_CULL)
+            # pairs actually binned (upstream's full count with LGM_RENDER_NO_CULL). The count takes no options: with
+            # LGM_RENDER_ANTIALIAS the forward bins with the compensated opacity o s <= o, and every step of the cull
+            # is monotone in the opacity, so the uncompensated count is a valid (upper-bound) capacity for it
+            # (include/lgm_render.h)
             cap = max(int(k[1 if options & nat.RENDER_NO_CULL else 0].item()), 1)
             ws_bytes = L.lgm_render_workspace_size_opts(B, V, N, H, W, cap, options)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)  # (sized above: not one nat.workspace question)
@@ -135,17 +138,19 @@ def deterministic_enabled() -> bool:
 
 
 def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, scale_modifier=1.0, clamp=False,
-              gt_images=None, gt_masks=None, deterministic=None, no_cull=False):
+              gt_images=None, gt_masks=None, deterministic=None, no_cull=False, antialias=False):
     """Functional form: returns (image [B,V,3,H,W], depth [B,V,1,H,W], alpha [B,V,1,H,W]). The image is
     unclamped unless clamp=True, which applies core/gs.py:87's clamp(0, 1) (and its gradient) inside the kernels.
     With gt_images [B,V,3,H,W] and gt_masks [B,V,1,H,W] a 4th output (loss_mse, mse_image, mse_alpha, psnr) holds
     LGM's training MSE terms (core/models.py:145-148,167), fused into the kernels; it is differentiable.
-    no_cull=True bins upstream's full 3-sigma tile rects (LGM_RENDER_NO_CULL: same outputs, more work)."""
+    no_cull=True bins upstream's full 3-sigma tile rects (LGM_RENDER_NO_CULL: same outputs, more work).
+    antialias=True compensates the opacity for the 0.3 px^2 dilation (LGM_RENDER_ANTIALIAS, include/lgm_render.h:
+    o sqrt(det cov / det(cov + 0.3 I)), the 3DGS rasteriser's `antialiasing`), forward and backward."""
     if not gaussians.is_cuda:  # CPU tensors: the torch path of BASELINE config 1 (lgm_amd/cpu.py), never the oracle
         from .cpu import render_cpu
         bgc = torch.as_tensor(bg, dtype=torch.float32).detach().cpu()
         out = render_cpu(gaussians, cam_view.cpu(), cam_view_proj.cpu(), bgc, tanfovx, tanfovy, int(H), int(W),
-                         scale_modifier, clamp=clamp)
+                         scale_modifier, clamp=clamp, antialias=antialias)
         if gt_images is None and gt_masks is None:
             return out
         gt_c = gt_images * gt_masks + bgc.view(1, 1, 3, 1, 1) * (1 - gt_masks)  # core/models.py:145
@@ -169,7 +174,8 @@ def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, sc
         gtm = gt_masks.to(dev, torch.float32).contiguous().detach()
         if tuple(gti.shape) != (B, V, 3, H, W) or tuple(gtm.shape) != (B, V, 1, H, W):
             raise ValueError("gt_images / gt_masks must be [B,V,3,H,W] / [B,V,1,H,W]")
-    options = (nat.RENDER_CLAMP_IMAGE if clamp else 0) | (nat.RENDER_NO_CULL if no_cull else 0)
+    options = (nat.RENDER_CLAMP_IMAGE if clamp else 0) | (nat.RENDER_NO_CULL if no_cull else 0) | \
+        (nat.RENDER_ANTIALIAS if antialias else 0)
     if deterministic_enabled() if deterministic is None else deterministic:
         options |= nat.RENDER_DETERMINISTIC
     out = _RasterizeBatched.apply(g, cv, cvp, bgt, float(tanfovx), float(tanfovy), float(scale_modifier),
@@ -188,14 +194,15 @@ def count_pairs(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, scal
 
 
 def forward_state(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, scale_modifier=1.0, lists=False,
-                  no_cull=False, records=False):
+                  no_cull=False, records=False, antialias=False):
     """Runs one forward and returns what it left in its workspace (numpy, one host sync), for parity tests and
     debugging -- the equivalent of reading upstream's saved buffers (radii, point_list/ranges, n_contrib):
       radii [B,V,N] int32; K_binned / K_reference (as count_pairs); tile_counts [B,V,T] int32;
       n_contrib, final_T [B,V,H,W]; with lists=True, ids[b][v] = the view's tile lists concatenated (tile-major,
       each in compositing order); with records=True, the compositing records P, Q [B,V,N,4] and rects [B,V,N,2]
-      (uint32) of lgm_render_records. no_cull=True bins upstream's full 3-sigma rects (LGM_RENDER_NO_CULL)."""
-    options = nat.RENDER_NO_CULL if no_cull else 0
+      (uint32) of lgm_render_records. no_cull=True bins upstream's full 3-sigma rects (LGM_RENDER_NO_CULL);
+      antialias=True renders with LGM_RENDER_ANTIALIAS (the records' L is then log2 of the compensated opacity)."""
+    options = (nat.RENDER_NO_CULL if no_cull else 0) | (nat.RENDER_ANTIALIAS if antialias else 0)
     L = nat.lib()
     g = gaussians.float().contiguous()
     dev = g.device
@@ -203,7 +210,8 @@ def forward_state(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, sc
     cv = cam_view.to(dev, torch.float32).contiguous()
     cvp = cam_view_proj.to(dev, torch.float32).contiguous()
     stream = nat.stream_of(dev)  # (the inspection copies below take a stream and no diag: plain lib() calls)
-    ws, ws_bytes = nat.workspace("lgm_render_workspace_size", dev, B, V, N, H, W, 0, min_bytes=0)
+    # (sized with the options: LGM_RENDER_ANTIALIAS's workspace is larger; the state read below lies before that)
+    ws, ws_bytes = nat.workspace("lgm_render_workspace_size_opts", dev, B, V, N, H, W, 0, options, min_bytes=0)
     bg = torch.zeros(3, device=dev)
     image = torch.empty(B, V, 3, H, W, device=dev)
     depth = torch.empty(B, V, 1, H, W, device=dev)
@@ -264,18 +272,20 @@ class GaussianRenderer:
         self.proj_matrix[2, 3] = 1
 
     def render(self, gaussians, cam_view, cam_view_proj, cam_pos, bg_color=None, scale_modifier=1, gt_images=None,
-               gt_masks=None):
+               gt_masks=None, antialias=None):
         """core/gs.py:31-98. gaussians [B,N,14]; cam_view, cam_view_proj [B,V,4,4]; cam_pos [B,V,3] (unused without
         SH, as upstream). Additive: with gt_images / gt_masks (the `images_output` / `masks_output` of
         core/models.py:140-141) the result also holds LGM's MSE loss terms, computed in the render kernels:
         "loss_mse" (differentiable: its backward seeds the render backward in-kernel), "mse_image", "mse_alpha"
-        and "psnr" (core/models.py:145-148,165-167)."""
+        and "psnr" (core/models.py:145-148,165-167). antialias (additive; None reads opt.antialias, default off):
+        the opacity compensation of rasterize(antialias=True)."""
         S = int(self.opt.output_size)
         bg = self.bg_color if bg_color is None else bg_color
         tan = float(self.tan_half_fov)
         # core/gs.py:87's clamp(0, 1) and its gradient are applied inside the kernels
         out = rasterize(gaussians, cam_view, cam_view_proj, bg, tan, tan, S, S, scale_modifier, clamp=True,
-                        gt_images=gt_images, gt_masks=gt_masks)
+                        gt_images=gt_images, gt_masks=gt_masks,
+                        antialias=bool(getattr(self.opt, "antialias", False) if antialias is None else antialias))
         res = {"image": out[0], "alpha": out[2], "depth": out[1]}
         if len(out) == 4:
             loss4 = out[3]

@@ -31,6 +31,9 @@ class Options:
     # augmentation probabilities of the provider (core/options.py:62-64), read by lgm_amd.data.build_batch
     prob_grid_distortion: float = 0.5
     prob_cam_jitter: float = 0.5
+    # opacity compensation of the rasteriser's 0.3 px^2 dilation (include/lgm_render.h LGM_RENDER_ANTIALIAS; the 3DGS
+    # rasteriser's `antialiasing`): read by GaussianRenderer.render at every call. Off: the rasteriser LGM pins.
+    antialias: bool = False
 
 
 _PRESETS = {

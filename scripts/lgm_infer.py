@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--frames", type=int, default=8, help="orbit frames to render")
     ap.add_argument("--render-size", type=int, default=256)
+    ap.add_argument("--antialias", action="store_true",
+                    help="orbit frames with the opacity compensation of the 0.3 px^2 dilation (Options.antialias)")
     ap.add_argument("--bf16", action="store_true", help="run the model under bf16 autocast (GPU)")
     ap.add_argument("--native-conv", action="store_true",
                     help="the UNet's stride-1 convolutions on the HIP kernel (16-bit on the GPU: with --bf16)")
@@ -65,7 +67,7 @@ def main():
     if dev.type == "cuda":
         from lgm_amd import build as B
         B.build()
-    opt = preset("big", output_size=a.render_size)
+    opt = preset("big", output_size=a.render_size, antialias=a.antialias)
     t = {}
     t0 = time.perf_counter()
     torch.manual_seed(a.seed)
