@@ -255,6 +255,14 @@ def diagnostics(profiler=None, render_counters=None, det_limit_log2=0):
         _diag_cur = prev
 
 
+def render_counter_words(B: int, V: int, N: int, H: int, W: int) -> int:
+    """uint64 words the render work-counter buffer of diagnostics(render_counters=...) must hold (csrc/render_layout.h
+    cnt_words, include/lgm_render.h; tests/test_render_layout.py holds the two equal): 8 aggregate words, then 8 per
+    (view, tile), 8 per binning record (B V ceil(N / 512) of them) and 4 per backward item (3 B V tiles + 16)."""
+    M = B * V * ((W + 15) // 16) * ((H + 15) // 16)
+    return 8 + 8 * M + 8 * B * V * ((N + 511) // 512) + 4 * (3 * M + 16)
+
+
 class KernelProfiler:
     """HIP events around every kernel liblgm_amd launches (on the launching stream) while the profiler is entered
     (`with prof:` = diagnostics(profiler=prof)). summary() -> {kernel: (launches, total_ms)}."""

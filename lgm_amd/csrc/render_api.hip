@@ -83,10 +83,33 @@ int check_ws(int B, int V, int N, int H, int W, const void *ws, size_t ws_bytes,
         lgm::set_error("invalid sizes (B=%d V=%d N=%d H=%d W=%d)", B, V, N, H, W);
         return LGM_E_INVALID;
     }
-    L = lgm::make_layout(B, V, N, H, W, cap, false);
+    // (without the call's options: every region the inspection entry points read sits ahead of the ones the options
+    // resize -- render_layout.h, checked by tests/test_render_layout.py)
+    L = lgm::make_layout(B, V, N, H, W, cap, 0);
     if (!ws || ws_bytes < L.total) {
         lgm::set_error("workspace too small (%zu < %zu)", ws_bytes, L.total);
         return LGM_E_WORKSPACE;
+    }
+    return LGM_OK;
+}
+// (the inspection entry points only read through the view)
+lgm::Workspace read_view(const void *ws, const lgm::Layout &L) { return lgm::Workspace((char *)ws, L); }
+
+// The part of a call's set-up that forward_impl and backward_impl share: the options, the antialias factors and the
+// fused loss's ground truth. `third` is the loss's third pointer (loss_out / d_loss): the three come together or not
+// at all.
+int setup_call(lgm::Dims &d, int options, const lgm::Workspace &w, const float *gt_images, const float *gt_masks,
+               const void *third, const char *pass, const char *third_name) {
+    d.options = options & ~LGM_RENDER_FUSED_LOSS;
+    d.aa_s = w.aa_s;
+    if (gt_images || gt_masks || third) {
+        if (!gt_images || !gt_masks || !third) {
+            lgm::set_error("fused loss%s needs gt_images, gt_masks and %s", pass, third_name);
+            return LGM_E_INVALID;
+        }
+        d.options |= LGM_RENDER_FUSED_LOSS;
+        d.gt_img = gt_images;
+        d.gt_mask = gt_masks;
     }
     return LGM_OK;
 }
@@ -96,14 +119,12 @@ int check_ws(int B, int V, int N, int H, int W, const void *ws, size_t ws_bytes,
 extern "C" {
 
 size_t lgm_render_workspace_size(int B, int V, int N, int H, int W, long long pair_capacity) {
-    if (B <= 0 || V <= 0 || N < 0 || H <= 0 || W <= 0) return 0;
-    return lgm::make_layout(B, V, N, H, W, pair_capacity).total;
+    return lgm_render_workspace_size_opts(B, V, N, H, W, pair_capacity, 0);
 }
 
 size_t lgm_render_workspace_size_opts(int B, int V, int N, int H, int W, long long pair_capacity, int options) {
     if (B <= 0 || V <= 0 || N < 0 || H <= 0 || W <= 0) return 0;
-    return lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0,
-                                               (options & LGM_RENDER_ANTIALIAS) != 0).total;
+    return lgm::make_layout(B, V, N, H, W, pair_capacity, options).total;
 }
 
 int lgm_render_count_pairs(int B, int V, int N, int H, int W, const float *gaussians, const float *cam_view,
@@ -119,13 +140,13 @@ int lgm_render_count_pairs(int B, int V, int N, int H, int W, const float *gauss
         lgm::set_error("null pairs_out");
         return LGM_E_INVALID;
     }
-    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, 1);
+    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, 1, 0);
     if (!workspace || workspace_bytes < L.total) {
         lgm::set_error("workspace too small for counting (%zu < %zu)", workspace_bytes, L.total);
         return LGM_E_WORKSPACE;
     }
-    return lgm::launch_binning(d, gaussians, cam_view, cam_view_proj, (char *)workspace, L, nullptr, pairs_out,
-                               true, (hipStream_t)stream);
+    return lgm::launch_binning(d, gaussians, cam_view, cam_view_proj, lgm::Workspace((char *)workspace, L), L, nullptr,
+                               pairs_out, true, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -145,8 +166,7 @@ static int forward_impl(int B, int V, int N, int H, int W, const float *gaussian
         lgm::set_error("null output pointer");
         return LGM_E_INVALID;
     }
-    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0,
-                                               (options & LGM_RENDER_ANTIALIAS) != 0);
+    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, options);
     if (!L.slot && !capacity_ok(L.cap)) {  // packed tile offsets are int32; slot offsets are 64-bit
         lgm::set_error("pair capacity %lld exceeds 2^31", L.cap);
         return LGM_E_INVALID;
@@ -155,27 +175,19 @@ static int forward_impl(int B, int V, int N, int H, int W, const float *gaussian
         lgm::set_error("workspace too small (%zu < %zu)", workspace_bytes, L.total);
         return LGM_E_WORKSPACE;
     }
-    char *ws = (char *)workspace;
-    d.options = options & ~LGM_RENDER_FUSED_LOSS;
-    if (options & LGM_RENDER_ANTIALIAS)
-        d.aa_s = lgm::acc_aa_factors((const char *)workspace + L.accum, B, V, N, (options & LGM_RENDER_DETERMINISTIC) != 0);
-    if (gt_images || gt_masks || loss_out) {
-        if (!gt_images || !gt_masks || !loss_out) {
-            lgm::set_error("fused loss needs gt_images, gt_masks and loss_out");
-            return LGM_E_INVALID;
-        }
-        d.options |= LGM_RENDER_FUSED_LOSS;
-        d.gt_img = gt_images;
-        d.gt_mask = gt_masks;
-        d.loss_part = (float *)(ws + L.lossp);
+    const lgm::Workspace w((char *)workspace, L);
+    rc = setup_call(d, options, w, gt_images, gt_masks, loss_out, "", "loss_out");
+    if (rc) return rc;
+    if (d.options & LGM_RENDER_FUSED_LOSS) {
+        d.loss_part = &w.lossp->x;
         d.loss_out = loss_out;
     }
     hipStream_t st = (hipStream_t)stream;
-    rc = lgm::launch_binning(d, gaussians, cam_view, cam_view_proj, ws, L, radii_out, stats_out, false, st);
+    rc = lgm::launch_binning(d, gaussians, cam_view, cam_view_proj, w, L, radii_out, stats_out, false, st);
     if (rc) return rc;
-    rc = lgm::launch_render_fwd(d, gaussians, bg, image, depth, alpha, ws, L, st);
+    rc = lgm::launch_render_fwd(d, gaussians, bg, image, depth, alpha, w, L, st);
     if (rc || !(d.options & LGM_RENDER_FUSED_LOSS)) return rc;
-    return lgm::launch_loss_reduce(d, ws, L, st);
+    return lgm::launch_loss_reduce(d, w, st);
 }
 
 static int backward_impl(int B, int V, int N, int H, int W, const float *gaussians, const float *cam_view,
@@ -193,28 +205,18 @@ static int backward_impl(int B, int V, int N, int H, int W, const float *gaussia
         lgm::set_error("null pointer in backward");
         return LGM_E_INVALID;
     }
-    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, (options & LGM_RENDER_DETERMINISTIC) != 0,
-                                               (options & LGM_RENDER_ANTIALIAS) != 0);
+    const lgm::Layout L = lgm::make_layout(B, V, N, H, W, pair_capacity, options);
     if (!workspace || workspace_bytes < L.total) {
         lgm::set_error("workspace too small (%zu < %zu)", workspace_bytes, L.total);
         return LGM_E_WORKSPACE;
     }
     if (N == 0) return LGM_OK;
-    d.options = options & ~LGM_RENDER_FUSED_LOSS;
-    if (options & LGM_RENDER_ANTIALIAS)
-        d.aa_s = lgm::acc_aa_factors((const char *)workspace + L.accum, B, V, N, (options & LGM_RENDER_DETERMINISTIC) != 0);
-    if (gt_images || gt_masks || d_loss) {
-        if (!gt_images || !gt_masks || !d_loss) {
-            lgm::set_error("fused loss backward needs gt_images, gt_masks and d_loss");
-            return LGM_E_INVALID;
-        }
-        d.options |= LGM_RENDER_FUSED_LOSS;
-        d.gt_img = gt_images;
-        d.gt_mask = gt_masks;
-        d.d_loss = d_loss;
-    }
+    const lgm::Workspace w((char *)workspace, L);
+    rc = setup_call(d, options, w, gt_images, gt_masks, d_loss, " backward", "d_loss");
+    if (rc) return rc;
+    d.d_loss = d_loss;
     return lgm::launch_render_bwd(d, gaussians, cam_view, cam_view_proj, bg, d_image, d_depth, d_alpha, d_gaussians,
-                                  d_means2D, (char *)workspace, L, (hipStream_t)stream);
+                                  d_means2D, w, L, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -270,14 +272,14 @@ int lgm_render_tile_lists(int B, int V, int N, int H, int W, const void *workspa
         return LGM_E_INVALID;
     }
     const int T = ((W + lgm::BX - 1) / lgm::BX) * ((H + lgm::BY - 1) / lgm::BY), M = B * V * T;
-    const char *ws = (const char *)workspace;
+    const lgm::Workspace w = read_view(workspace, L);
     const long long stride = L.slot ? (long long)N : -1LL;
-    const int *ts = (const int *)(ws + L.tile_start), *tc = (const int *)(ws + L.tile_count);
     hipStream_t st = (hipStream_t)stream;
-    LGM_LAUNCH("k_tile_counts", st, (k_tile_counts<<<(M + 255) / 256, 256, 0, st>>>(M, stride, ts, tc, tile_counts_out)));
+    LGM_LAUNCH("k_tile_counts", st, (k_tile_counts<<<(M + 255) / 256, 256, 0, st>>>(M, stride, w.tile_start, w.tile_count,
+                                                                                    tile_counts_out)));
     if (ids_out && N > 0)
-        LGM_LAUNCH("k_tile_ids", st, (k_tile_ids<<<M, 256, 0, st>>>(stride, ts, tc,
-                                     (const unsigned long long *)(ws + L.pairs), offsets, ids_out)));
+        LGM_LAUNCH("k_tile_ids", st, (k_tile_ids<<<M, 256, 0, st>>>(stride, w.tile_start, w.tile_count, w.pairs, offsets,
+                                                                    ids_out)));
     return LGM_OK;
 }
 
@@ -288,13 +290,13 @@ int lgm_render_pixel_state(int B, int V, int N, int H, int W, const void *worksp
     int rc = check_ws(B, V, N, H, W, workspace, workspace_bytes, pair_capacity, L);
     if (rc) return rc;
     const size_t P = (size_t)B * V * H * W;
-    const char *ws = (const char *)workspace;
+    const lgm::Workspace w = read_view(workspace, L);
     hipStream_t st = (hipStream_t)stream;
-    if (n_contrib_out && hipMemcpyAsync(n_contrib_out, ws + L.n_contrib, P * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    if (n_contrib_out && hipMemcpyAsync(n_contrib_out, w.n_contrib, P * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         lgm::set_error("hipMemcpyAsync failed");
         return LGM_E_HIP;
     }
-    if (final_T_out && hipMemcpyAsync(final_T_out, ws + L.final_T, P * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    if (final_T_out && hipMemcpyAsync(final_T_out, w.final_T, P * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         lgm::set_error("hipMemcpyAsync failed");
         return LGM_E_HIP;
     }
@@ -308,12 +310,12 @@ int lgm_render_records(int B, int V, int N, int H, int W, const void *workspace,
     int rc = check_ws(B, V, N, H, W, workspace, workspace_bytes, pair_capacity, L);
     if (rc) return rc;
     const size_t BVN = (size_t)B * V * N;
-    const char *ws = (const char *)workspace;
+    const lgm::Workspace w = read_view(workspace, L);
     hipStream_t st = (hipStream_t)stream;
-    const struct { void *dst; size_t off, bytes; } cp[3] = {
-        {P_out, L.gP, BVN * 16}, {Q_out, L.gQ, BVN * 16}, {rects_out, L.rects, BVN * 8}};
+    const struct { void *dst; const void *src; size_t bytes; } cp[3] = {
+        {P_out, w.gP, BVN * 16}, {Q_out, w.gQ, BVN * 16}, {rects_out, w.rects, BVN * 8}};
     for (const auto &c : cp) {
-        if (c.dst && c.bytes && hipMemcpyAsync(c.dst, ws + c.off, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        if (c.dst && c.bytes && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
             lgm::set_error("hipMemcpyAsync failed");
             return LGM_E_HIP;
         }

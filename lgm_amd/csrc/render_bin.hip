@@ -126,8 +126,8 @@ __device__ void center_order(int gx, int T, int *__restrict__ corder, int *hk) {
     for (int t = tid; t < T; t += BIN_THREADS) corder[atomicAdd(&hk[key(t)], 1)] = t;
 }
 
-// STATS: the pair statistics (misc[0..1] <- emitted and reference (Gaussian, tile) pair counts), read only through
-// stats_out and by the count-only pass. STAMPS: the per-workgroup phase stamps of lgm_diag.render_counters. Both
+// STATS: the pair statistics (pair_counts[0..1], the misc block's MISC_PAIRS <- emitted and reference (Gaussian,
+// tile) pair counts), read only through stats_out and by the count-only pass. STAMPS: the per-workgroup phase stamps of lgm_diag.render_counters. Both
 // are compile-time: a training or inference render asks for neither, and their state (a 64-bit wave sum per view,
 // 64-bit stamp values live across the view loop) cost the production kernel a third workgroup per CU.
 template <int MODE, bool STATS, bool STAMPS>
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin
     Dims d, const float *__restrict__ gauss, const float *__restrict__ views, const float *__restrict__ projs,
     float4 *__restrict__ gP, float4 *__restrict__ gQ, uint2 *__restrict__ rects, int *__restrict__ radii_out,
     int *__restrict__ tile_count, const int *__restrict__ tile_start, unsigned long long *__restrict__ pairs,
-    long long slot_stride, unsigned long long *__restrict__ misc, float *__restrict__ accum,
+    long long slot_stride, unsigned long long *__restrict__ pair_counts, float *__restrict__ accum,
     int *__restrict__ corder) {
     extern __shared__ int hist[];  // [T] per-tile hit counts, [T] reserved global bases, [T] fallback cursors
     __shared__ BinRec srec[BIN_THREADS];
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin
     __shared__ unsigned long long s_ph[4];  // (STAMPS)
     unsigned long long *stamp = nullptr;
     if constexpr (STAMPS) {
-        stamp = d.counters + 8 + 8 * (size_t)d.BV * T + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+        stamp = d.counters + cnt_bin0(d.BV, T) + CNT_BIN * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
         if (tid == 0) {
             s_ph[0] = s_ph[1] = s_ph[2] = 0;
             stamp[0] = s_ph[3] = __builtin_amdgcn_s_memrealtime();
@@ -216,8 +216,8 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin
                 const bool side = !(d.options & LGM_RENDER_DETERMINISTIC) && rec_needle(rp.z, rp.w, rq.x);
                 rects[k] = make_uint2((unsigned)o.x0 | ((unsigned)o.y0 << 16),
                                       (unsigned)o.x1 | ((unsigned)o.y1 << 16) | (side ? 0x80000000u : 0u));
-                if (side) {  // the record's fp64 conic accumulators (acc_side_offset)
-                    double *sd = reinterpret_cast<double *>(accum + acc_side_offset(d.B, d.V, d.N)) + k * 3;
+                if (side) {  // the record's fp64 conic accumulators (AccumLayout::needle)
+                    double *sd = reinterpret_cast<double *>(accum) + accum_needle_dbl(d.B, d.V, d.N, k, 0);
                     sd[0] = 0.0; sd[1] = 0.0; sd[2] = 0.0;
                 }
             } else {
@@ -371,15 +371,15 @@ __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(bin
     }
     }  // batches
     if (STATS && tid == 0) {
-        atomicAdd(&misc[0], s_tot[0]);
-        atomicAdd(&misc[1], s_tot[1]);
+        atomicAdd(&pair_counts[0], s_tot[0]);
+        atomicAdd(&pair_counts[1], s_tot[1]);
     }
     if (corder && blockIdx.x == 0 && blockIdx.y == 0) center_order(d.gx, T, corder, hist);
 }
 
 // k_aa_factor (LGM_RENDER_ANTIALIAS only): grid (ceil(N / 256), B * V), block 256. The opacity factor
 //   s = sqrt(min(1, fmax(2.5e-5, det0 / det))),  det0 = a0 c0 - b^2,  det = (a0 + 0.3)(c0 + 0.3) - b^2   (lgm_render.h)
-// of every (view, Gaussian), written as fp32 to the workspace (acc_aa_factors) ahead of the binning; preprocess_view
+// of every (view, Gaussian), written as fp32 to the workspace (AccumLayout::aa_s) ahead of the binning; preprocess_view
 // and k_preproc_bwd read it. It restates cov2d's sums -- the 1.3 tan-fov clamp, T = W J, Sigma = M^T M, a0 = T0 . Sigma
 // T0, b, c0 -- in fp64 on the same fp32 inputs (and upstream's fp32 literals: 0.3f, 1.3f tan), because det0 cancels:
 // for an elongated splat a0 c0 / det0 reaches hundreds, and the fp32 rounding a0, b and c0 carry is amplified by it
@@ -910,13 +910,13 @@ __global__ __launch_bounds__(RS_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
     tile_range(tile, slot_stride, tile_start, tile_count, base, n);
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     if (counters && threadIdx.x == 0) {  // per-workgroup timeline + bucket size (see lgm_diag.render_counters)
-        counters[8 + 8 * (size_t)tile + 4] = t_start;
-        counters[8 + 8 * (size_t)tile + 6] = (unsigned long long)n;
+        counters[cnt_tile(tile) + 4] = t_start;
+        counters[cnt_tile(tile) + 6] = (unsigned long long)n;
     }
     sort_tile(base, n, pairs);
     if (counters) {
         __syncthreads();
-        if (threadIdx.x == 0) counters[8 + 8 * (size_t)tile + 5] = __builtin_amdgcn_s_memrealtime();
+        if (threadIdx.x == 0) counters[cnt_tile(tile) + 5] = __builtin_amdgcn_s_memrealtime();
     }
 }
 
@@ -924,43 +924,33 @@ __global__ __launch_bounds__(RS_THREADS) __attribute__((amdgpu_waves_per_eu(8)))
 
 // ------------------------------------------------------------------------------------------------------------
 int launch_binning(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
-                   char *ws, const Layout &L, int *radii_out, long long *stats_out, bool count_only,
+                   const Workspace &w, const Layout &L, int *radii_out, long long *stats_out, bool count_only,
                    hipStream_t st) {
     const size_t M = (size_t)d.BV * d.T;
-    // tile counters and the misc counters are adjacent in the layout: one memset
-    if (hipMemsetAsync(ws + L.tile_count, 0, L.misc + 64 - L.tile_count, st) != hipSuccess) {
+    const Region bin_clear = L.bin_clear();  // the tile counters and the misc counters
+    if (hipMemsetAsync(w.range(bin_clear), 0, bin_clear.bytes, st) != hipSuccess) {
         set_error("hipMemsetAsync failed");
         return LGM_E_HIP;
     }
-    float4 *gP = (float4 *)(ws + L.gP), *gQ = (float4 *)(ws + L.gQ);
-    uint2 *rects = (uint2 *)(ws + L.rects);
-    int *tcount = (int *)(ws + L.tile_count), *tstart = (int *)(ws + L.tile_start);
-    unsigned long long *pairs = (unsigned long long *)(ws + L.pairs), *misc = (unsigned long long *)(ws + L.misc);
-    float *accum = (float *)(ws + L.accum);
-    // LGM_RENDER_ANTIALIAS: the per-view opacity partials (acc_aa_offset) start at zero; the other accumulators are
-    // zeroed by k_render_fwd's epilogue and, the fp64 side block, by k_bin
-    // and the factors themselves are written ahead of the count pass and the binning (k_aa_factor). (The count-only
-    // pass of lgm_render_count_pairs takes no options; its workspace has no such block.)
+    // LGM_RENDER_ANTIALIAS: the per-view opacity partials start at zero here (who zeroes the other accumulators:
+    // AccumLayout), and the factors themselves are written ahead of the count pass and the binning (k_aa_factor).
+    // (The count-only pass of lgm_render_count_pairs takes no options; its workspace has no such block.)
     if (count_only && (d.options & LGM_RENDER_ANTIALIAS)) {
         set_error("the counting pass takes no LGM_RENDER_ANTIALIAS");
         return LGM_E_INVALID;
     }
     if ((d.options & LGM_RENDER_ANTIALIAS) && d.N > 0) {
-        const bool det = (d.options & LGM_RENDER_DETERMINISTIC) != 0;
-        if (hipMemsetAsync(ws + L.accum + acc_clear_bytes(d.B, d.V, d.N, det, false), 0,
-                           acc_clear_bytes(d.B, d.V, d.N, det, true) - acc_clear_bytes(d.B, d.V, d.N, det, false),
-                           st) != hipSuccess) {
+        if (hipMemsetAsync(w.accum_range(L.acc.aa_part), 0, L.acc.aa_part.bytes, st) != hipSuccess) {
             set_error("hipMemsetAsync failed");
             return LGM_E_HIP;
         }
         LGM_LAUNCH("k_aa_factor", st, (k_aa_factor<<<dim3((d.N + 255) / 256, d.BV), 256, 0, st>>>(
-                                          d, gaussians, cam_view,
-                                          const_cast<float *>(d.aa_s))));
+                                          d, gaussians, cam_view, w.aa_s)));
     }
     const size_t lds =d.T <= LDS_HIST_MAX ? 3 * (size_t)d.T * 4 : 0;
     // k_sort's centre-first tile table (the first T ints of the order buffer; the binning histogram's 3T ints of LDS
     // hold its counting sort)
-    int *corder = lds && d.T >= 8 ? (int *)(ws + L.order) : nullptr;
+    int *corder = lds && d.T >= 8 ? w.order : nullptr;
     dim3 grid((d.N + BIN_G - 1) / BIN_G, d.B * ((d.V + BIN_ITERS - 1) / BIN_ITERS));
     // the pair statistics and the phase stamps are separate instantiations (k_bin): a render that asks for neither
     // runs the kernel without their state
@@ -968,34 +958,34 @@ int launch_binning(const Dims &d, const float *gaussians, const float *cam_view,
     if (d.N > 0) {
         if (count_only || !L.slot) {
             LGM_LAUNCH("k_bin_count", st, (bin_kernel<COUNT>(stats, stamps)<<<grid, BIN_THREADS, lds, st>>>(
-                       d, gaussians, cam_view, cam_view_proj, gP, gQ, rects, nullptr, tcount, tstart, pairs, 0, misc,
-                       accum, nullptr)));
+                       d, gaussians, cam_view, cam_view_proj, w.gP, w.gQ, w.rects, nullptr, w.tile_count,
+                       w.tile_start, w.pairs, 0, w.pair_counts, w.accum, nullptr)));
         }
         if (!count_only) {
             if (L.slot) {
                 LGM_LAUNCH("k_bin", st, (bin_kernel<EMIT_SLOT>(stats, stamps)<<<grid, BIN_THREADS, lds, st>>>(
-                           d, gaussians, cam_view, cam_view_proj, gP, gQ, rects, radii_out, tcount, tstart, pairs,
-                           (long long)d.N, misc, accum, corder)));
+                           d, gaussians, cam_view, cam_view_proj, w.gP, w.gQ, w.rects, radii_out, w.tile_count,
+                           w.tile_start, w.pairs, (long long)d.N, w.pair_counts, w.accum, corder)));
             } else {
-                LGM_LAUNCH("k_scan", st, (k_scan<<<1, 1024, 0, st>>>(tcount, (int)M, tstart)));
-                if (hipMemsetAsync(ws + L.tile_count, 0, L.misc + 64 - L.tile_count, st) != hipSuccess) {
+                LGM_LAUNCH("k_scan", st, (k_scan<<<1, 1024, 0, st>>>(w.tile_count, (int)M, w.tile_start)));
+                if (hipMemsetAsync(w.range(bin_clear), 0, bin_clear.bytes, st) != hipSuccess) {
                     set_error("hipMemsetAsync failed");
                     return LGM_E_HIP;
                 }
                 LGM_LAUNCH("k_bin", st, (bin_kernel<EMIT_PACKED>(stats, stamps)<<<grid, BIN_THREADS, lds, st>>>(
-                           d, gaussians, cam_view, cam_view_proj, gP, gQ, rects, radii_out, tcount, tstart, pairs, 0,
-                           misc, accum, corder)));
+                           d, gaussians, cam_view, cam_view_proj, w.gP, w.gQ, w.rects, radii_out, w.tile_count,
+                           w.tile_start, w.pairs, 0, w.pair_counts, w.accum, corder)));
             }
             LGM_LAUNCH("k_sort", st, (k_sort<<<(unsigned)M, RS_THREADS, RS_LDS, st>>>(
-                                         (int)M, L.slot ? (long long)d.N : -1LL, tstart, tcount, pairs, d.counters,
-                                         d.BV, d.T, corder)));
+                                         (int)M, L.slot ? (long long)d.N : -1LL, w.tile_start, w.tile_count, w.pairs,
+                                         d.counters, d.BV, d.T, corder)));
         }
     }
-    if (d.N == 0 && !L.slot && hipMemsetAsync(ws + L.tile_start, 0, (M + 1) * 4, st) != hipSuccess) {
+    if (d.N == 0 && !L.slot && hipMemsetAsync(w.tile_start, 0, (M + 1) * 4, st) != hipSuccess) {
         set_error("hipMemsetAsync failed");  // packed mode with no Gaussians: every tile range is empty
         return LGM_E_HIP;
     }
-    if (stats_out && hipMemcpyAsync(stats_out, ws + L.misc, 16, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    if (stats_out && hipMemcpyAsync(stats_out, w.pair_counts, MISC_PAIRS_N * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("hipMemcpyAsync failed");
         return LGM_E_HIP;
     }

@@ -1,4 +1,5 @@
-// lgm_amd/csrc/render_common.h -- shared constants, workspace layout and device math of the render path.
+// lgm_amd/csrc/render_common.h -- shared constants, the typed view of the workspace and device math of the render
+// path. (Where the workspace's bytes live: render_layout.h.)
 //
 // Numerics restate SURVEY.md §2.3 (the upstream algorithm behind core/gs.py:58-85; CPU restatement in
 // oracle/raster_oracle.c): 0.3 dilation, 1.3 tanfov clamp inside J, depth cull 0.2, radius = ceil(3 sqrt(lmax))
@@ -8,69 +9,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "lgm_render.h"
+#include "render_layout.h"
 #include "work_split.h"
 
 namespace lgm {
 
-constexpr int BX = 16, BY = 16, TILE_PIX = BX * BY;  // 256 pixels per tile = 4 wavefronts (8x8 quadrants)
-constexpr int NACC = 10;  // gradient partials per (view, Gaussian): mean2D(2) conic(3) opacity rgb(3) depth
-// Accumulator layout (elements: fp32, or int64 fixed point in deterministic mode): the view-dependent partials
-// (mean2D, conic, depth) per (view, Gaussian) in records of NACC_V, then the view-independent ones (opacity,
-// colour) per (scene, Gaussian) in records of NACC_S -- the views of a scene add into one record, so the forward
-// zeroes and k_preproc_bwd reads 24 + 16 / V bytes per (view, Gaussian) instead of 40.
-constexpr int NACC_V = 6, NACC_S = 4;
-__host__ __device__ __forceinline__ size_t acc_index(int q, size_t bvN_i, size_t bN_i, size_t BVN) {
-    return q < 5 ? bvN_i * NACC_V + q : q < 9 ? BVN * NACC_V + bN_i * NACC_S + (q - 5) : bvN_i * NACC_V + 5;
-}
-__host__ __device__ inline size_t acc_elems(size_t B, size_t V, size_t N) { return B * V * N * NACC_V + B * N * NACC_S; }
-// Float mode: the conic partials (q = 2..4) of NEEDLE records go to fp64 side accumulators, 3 per (view, Gaussian),
-// placed after the fp32 ones (float offset acc_side_offset, 8-B aligned). A needle is a record whose conic
-// condition (A + C)^2 / (AC - B^2) exceeds ACC_NEEDLE (or is not positive definite), decided on the
-// stored record (rec_needle) identically by the binning, the backward's flush and the preprocess backward (via a
-// flag in bit 31 of the record's rect).
-__host__ __device__ inline size_t acc_side_offset(size_t B, size_t V, size_t N) { return (acc_elems(B, V, N) + 1) & ~(size_t)1; }
-// LGM_RENDER_ANTIALIAS: the opacity partial per (view, Gaussian) instead of per scene (the preprocess backward needs
-// dL/do^ of each view: lgm_render.h), one element (fp32, or int64 in deterministic mode) per (view, Gaussian), placed
-// after everything above -- the fp64 side block in float mode -- and then the factors s themselves, one fp32 per
-// (view, Gaussian) (k_aa_factor writes them ahead of the binning; the binning and the preprocess backward read them).
-// Both are present only with the bit. acc_aa_offset: the partials' offset in elements; acc_clear_bytes: the bytes a
-// repeated backward clears (every accumulator, the partials included, not the factors); acc_bytes: the whole block.
-__host__ __device__ inline size_t acc_aa_offset(size_t B, size_t V, size_t N, bool det) {
-    return det ? acc_elems(B, V, N) : acc_side_offset(B, V, N) + B * V * N * 6;
-}
-__host__ __device__ inline size_t acc_clear_bytes(size_t B, size_t V, size_t N, bool det, bool aa) {
-    return (det ? acc_elems(B, V, N) * 8 : acc_side_offset(B, V, N) * 4 + B * V * N * 3 * 8) +
-           (aa ? B * V * N * (det ? 8 : 4) : 0);
-}
-__host__ __device__ inline size_t acc_bytes(size_t B, size_t V, size_t N, bool det, bool aa) {
-    return acc_clear_bytes(B, V, N, det, aa) + (aa ? B * V * N * 4 : 0);
-}
-// the factors of a call with the bit (accum: the accumulator block's start)
-__host__ __device__ __forceinline__ const float *acc_aa_factors(const void *accum, size_t B, size_t V, size_t N, bool det) {
-    return reinterpret_cast<const float *>(static_cast<const char *>(accum) + acc_clear_bytes(B, V, N, det, true));
-}
-// Deterministic mode's per-flush overflow bound (k_render_bwd): in that mode an accumulator takes at most one flush
-// per tile list its Gaussian appears in -- one work item per tile, an entry once per list. A per-view record (mean2D,
-// conic, depth) sees the T tiles of its view; a per-scene record (opacity, colour: acc_index q = 5..8) the V * T
-// tiles of all views of its scene. With every flush |a| <= 2^62 / 2^ceil(log2 flushes), no sum of them reaches 2^62,
-// whatever their signs, so int64 cannot wrap. (The design value of a flush is <= ~2^51: DET_BITS below.)
-__host__ __device__ inline int det_flush_limit_log2(int V, int T, bool scene_record) {
-    const long long f = scene_record ? (long long)V * T : (long long)T;
-    int c = 0;
-    while ((1ll << c) < f) c++;  // ceil(log2 f)
-    return 62 - c;
-}
 constexpr int LDS_HIST_MAX = 8192;                   // tiles per view for the LDS-histogram binning path
 constexpr float LOG2E = 1.4426950408889634f;
 
-inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
-// Deterministic mode takes no backward checkpoints: one backward work item per tile, so how a tile's walk splits into
-// work items cannot depend on which tiles won the shared pool's slot counters (a racing split changes the backward's
-// per-chunk partials in their last bits). A per-tile checkpoint quota was measured (profiles/r03/ab_det):
-// deterministic k_render_bwd 1950 / 1306 / 955 / 787 / 685 / 650 us at quota 16 / 8 / 4 / 2 / 1 / 0 (float mode
-// 626) -- in the fixed-point mode the split costs more than its load balance returns.
 // Float mode's gradient accumulators: fp32, and fp64 for the conic partials of needle-like records. A needle's conic
 // partials from different tiles and views largely cancel and the cov2D inverse amplifies what is left (conditions
 // 1e3-2e4), so fp32 atomic sums made its scale / rotation gradients a draw of the atomic order (single runs up to ~3x
@@ -78,80 +28,6 @@ inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 // order-independent to ~2^-50 of the partials (the deterministic mode's int64 sums are exact). Measured: all
 // accumulators fp64 +37 us per pool step, the needle side accumulators +24 us (profiles/r03/ab_acc_side).
 constexpr float ACC_NEEDLE = 300.0f;  // conic condition above which a record's conic partials are summed in fp64
-
-// Workspace layout. Pair storage `pairs` holds one u64 key (depth_bits << 32 | gaussian id) per (Gaussian, tile)
-// pair; after sorting, the tile's u32 ids are written in place at the start of its range.
-//   slot mode   (pair_capacity <= 0): tile (bv, t) owns pairs[(bv*T + t) * N, +N): no counting pass, no scan.
-//   packed mode (pair_capacity  > 0): tiles are packed by an exclusive scan of exact counts.
-struct Layout {
-    size_t gP, gQ, rects, tile_count, tile_start, order, pairs, final_T, n_contrib, wlast, cfin, ck, cklist, nck, cmask,
-        accum, lossp, lossw, detmax, misc, total;
-    long long cap;
-    int ck_region;  // backward checkpoint slots per region (8 regions; the forward shards tiles over them)
-    int ck_slots;   // checkpoint slots in all: 8 ck_region (none in deterministic mode)
-    bool slot;
-};
-
-// det (LGM_RENDER_DETERMINISTIC): the per-view gradient accumulators are int64 fixed point (data-scaled units, see
-// render_raster.hip det_norm) instead of fp32: integer atomics commute, so the backward's sums do not depend on the
-// order of its work items.
-// Backward work items span 2^ck_shift staged forward chunks (of TILE_PIX entries): 2 chunks for launches of at least
-// CK_LONG_TILES tiles, where the many short checkpoint items run at the end of k_render_bwd at about half its slots
-// (each workgroup hand-over idles a slot for a few us); one for smaller launches, whose head items already exceed
-// one residency round. Pool (12,288 tiles): k_render_bwd 599 -> 588 us and k_render_fwd -6 us (fewer checkpoints);
-// one cfg3 scene (1,536 tiles) with 2: bwd 92.7 -> 102.8 us (profiles/r06/ab_bwd_cks).
-#ifndef LGM_CK_LONG_TILES
-#define LGM_CK_LONG_TILES 4096
-#endif
-constexpr size_t CK_LONG_TILES = LGM_CK_LONG_TILES;
-#ifdef LGM_CK_SHIFT0  // (A/B: one chunk per item at every size)
-__host__ __device__ __forceinline__ int ck_shift_for(size_t) { return 0; }
-#else
-__host__ __device__ __forceinline__ int ck_shift_for(size_t tiles) { return tiles >= CK_LONG_TILES ? 1 : 0; }
-#endif
-
-inline Layout make_layout(int B, int V, int N, int H, int W, long long pair_capacity, bool det = false,
-                          bool aa = false) {
-    const size_t BV = (size_t)B * V, T = (size_t)((W + BX - 1) / BX) * ((H + BY - 1) / BY), P = (size_t)H * W;
-    Layout L;
-    L.slot = pair_capacity <= 0;
-    L.cap = L.slot ? (long long)(BV * T * (size_t)N) : pair_capacity;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes); return r; };
-    L.gP = take(BV * N * 16);  // (x, y, A, B): centre and conic A, B (one 16-B row per (view, Gaussian))
-    L.gQ = take(BV * N * 16);  // (C, opacity, tau, depth)
-    L.rects = take(BV * N * 8);
-    L.tile_count = take(BV * T * 4);
-    L.misc = take(64);  // right after tile_count: the binning clears both with one memset (u64 [0..1]: pair
-                        // counts of k_bin; u32 [4..11]: the backward-checkpoint region counters; u32 [12]: the
-                        // fused loss reduction's arrival counter; u32 [13]: deterministic mode's saturated flushes)
-    L.tile_start = take((BV * T + 1) * 4);
-    L.order = take(T * 4);  // k_sort's centre-first tile table (center_order)
-    L.pairs = take((size_t)L.cap * 8);
-    L.final_T = take(BV * P * 4);
-    L.n_contrib = take(BV * P * 4);
-    L.wlast = take(BV * T * 16);  // per tile: the four waves' largest last contributor (forward -> backward)
-    L.cfin = take(BV * P * 16);  // per-pixel pre-background colour and depth totals (forward -> backward)
-    // backward checkpoints (k_render_fwd -> k_render_bwd), 5 planes of 256 floats each, in 8 regional pools (a
-    // region is one eighth of the launch's tiles). k_render_bwd launches one workgroup per slot, and an unused slot's
-    // workgroup still pays a dispatch and a counter round trip before it exits: at 2 slots per tile the pool (8 scenes,
-    // ~0.53 used per tile) left 18k such workgroups and cost k_render_bwd ~15 us. A region holds min(2 per tile,
-    // 0.75 per tile + 256): the 8-scene pool 1,408 per region (its busiest uses ~860), one cfg3 scene keeps 2 per
-    // tile (384: its central regions need ~1 per tile), BASELINE config 2 keeps 64 (profiles/r06/ab_bwd_ckcap,
-    // abfull_cap). A full region leaves the rest of a tile's walk to its last checkpointed item (slower, same result).
-    L.ck_region = (int)std::min((2 * BV * T + 7) / 8, ((3 * BV * T / 4) >> ck_shift_for(BV * T)) / 8 + 1 + 256);
-    L.ck_slots = det ? 0 : 8 * L.ck_region;
-    L.ck = take((size_t)L.ck_slots * 5 * TILE_PIX * 4);
-    L.cklist = take((size_t)L.ck_slots * 8);
-    L.nck = take(BV * T * 4);
-    L.cmask = take(BV * P);
-    L.accum = take(acc_bytes(B, V, N, det, aa));  // (aa: + the per-view opacity partials, acc_aa_offset)
-    L.lossp = take(BV * T * 2 * 4);  // per-tile sums of squared image / alpha residuals (fused loss)
-    L.lossw = take(((BV * T + 2047) / 2048) * 16);  // their per-workgroup double2 partials (k_loss_reduce)
-    L.detmax = take(64 * 4);  // deterministic mode: max |dL/dpixel| over the seeds, in 64 atomicMax slots
-    L.total = o;
-    return L;
-}
 
 struct Dims {
     int B, V, N, H, W, gx, gy, T, BV;
@@ -167,9 +43,49 @@ struct Dims {
     float *loss_part;  // workspace: per-tile (image, alpha) sums of squared residuals
     float *loss_out;   // DEVICE float[4]: loss_mse, mse_image, mse_alpha, psnr
     const float *d_loss;  // DEVICE float[2]: dL/dmse_image, dL/dmse_alpha
-    // LGM_RENDER_ANTIALIAS: the workspace's opacity factors s [BV, N] (acc_aa_factors; k_aa_factor writes them ahead
+    // LGM_RENDER_ANTIALIAS: the workspace's opacity factors s [BV, N] (Workspace::aa_s; k_aa_factor writes them ahead
     // of the binning), else null
     const float *aa_s;
+};
+
+// The workspace as typed pointers, built once per call: the one place that casts into it. (The kernels take the
+// pointers one by one: a struct argument would change their kernarg layout and drop the __restrict__ information.)
+struct Workspace {
+    char *base;
+    float4 *gP, *gQ;
+    uint2 *rects;
+    int *tile_count, *tile_start, *order;
+    unsigned long long *pairs;
+    float *final_T;
+    int *n_contrib, *wlast;
+    float4 *cfin;
+    float *ck;
+    int2 *cklist;
+    int *nck;
+    unsigned char *cmask;
+    float *accum;      // the accumulator block (AccumLayout) as fp32 elements; the kernels recast it per region
+    float4 *accum16;   // the same block as the 16-B units k_render_fwd's epilogue zeroes (AccumLayout::fwd_zero)
+    float2 *lossp;
+    double2 *lossw;
+    unsigned *detmax;
+    unsigned long long *pair_counts;                  // misc: MISC_PAIRS
+    unsigned *ck_counters, *loss_arrival, *det_sat;  // misc: MISC_CK_REGION, MISC_LOSS_ARRIVAL, MISC_DET_SAT
+    float *aa_s;  // LGM_RENDER_ANTIALIAS: the factors (AccumLayout::aa_s), else null
+    Workspace(char *ws, const Layout &L) : base(ws) {
+        auto at = [ws](auto *&p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(ws + off); };
+        at(gP, L.gP); at(gQ, L.gQ); at(rects, L.rects);
+        at(tile_count, L.tile_count); at(tile_start, L.tile_start); at(order, L.order); at(pairs, L.pairs);
+        at(final_T, L.final_T); at(n_contrib, L.n_contrib); at(wlast, L.wlast); at(cfin, L.cfin);
+        at(ck, L.ck); at(cklist, L.cklist); at(nck, L.nck); at(cmask, L.cmask);
+        at(accum, L.accum); at(accum16, L.accum);
+        at(lossp, L.lossp); at(lossw, L.lossw); at(detmax, L.detmax);
+        at(pair_counts, L.misc + MISC_PAIRS * 8); at(ck_counters, L.misc + MISC_CK_REGION * 4);
+        at(loss_arrival, L.misc + MISC_LOSS_ARRIVAL * 4); at(det_sat, L.misc + MISC_DET_SAT * 4);
+        aa_s = nullptr;
+        if (L.acc.aa_s.bytes) at(aa_s, L.accum + L.acc.aa_s.off);
+    }
+    char *range(const Region &r) const { return base + r.off; }  // a range of the workspace (Layout::bin_clear)
+    char *accum_range(const Region &r) const { return reinterpret_cast<char *>(accum) + r.off; }  // of AccumLayout
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -304,7 +220,7 @@ __device__ __forceinline__ float4 rec_p(float x, float y, float A, float B) {
 __device__ __forceinline__ float4 rec_q(float C, float opacity, float tau, float depth) {
     return make_float4(-KQ * C, opacity > 0.f ? log2f(opacity) : -INFINITY, tau >= 3.0e38f ? tau : KQ * tau, depth);
 }
-// Needle-like record (see acc_side_offset): on the stored pre-scaled conic A', B', C' (the condition is
+// Needle-like record (see AccumLayout::needle): on the stored pre-scaled conic A', B', C' (the condition is
 // scale-invariant: (A' + C')^2 / (A'C' - B'^2 / 4) = (A + C)^2 / (AC - B^2)).
 // FP contraction OFF: k_bin evaluates it on the record still in registers (right after the multiplications that
 // form A', B', C'), k_render_bwd on the record loaded back from memory; with contraction a fused multiply-add could
@@ -478,15 +394,15 @@ __device__ __forceinline__ void tile_pixel(int t, int &lx, int &ly) {
 
 // ---- host launchers (defined in render_bin.hip / render_raster.hip)
 int launch_binning(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
-                   char *ws, const Layout &L, int *radii_out, long long *stats_out, bool count_only,
+                   const Workspace &w, const Layout &L, int *radii_out, long long *stats_out, bool count_only,
                    hipStream_t st);
 int launch_render_fwd(const Dims &d, const float *gaussians, const float *bg, float *image, float *depth,
-                      float *alpha, char *ws, const Layout &L, hipStream_t st);
+                      float *alpha, const Workspace &w, const Layout &L, hipStream_t st);
 // the fused loss's final reduction (after launch_render_fwd with LGM_RENDER_FUSED_LOSS): d.loss_out receives
 // (loss_mse, mse_image, mse_alpha, psnr)
-int launch_loss_reduce(const Dims &d, char *ws, const Layout &L, hipStream_t st);
+int launch_loss_reduce(const Dims &d, const Workspace &w, hipStream_t st);
 int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
                       const float *bg, const float *d_image, const float *d_depth, const float *d_alpha,
-                      float *d_gaussians, float *d_means2D, char *ws, const Layout &L, hipStream_t st);
+                      float *d_gaussians, float *d_means2D, const Workspace &w, const Layout &L, hipStream_t st);
 
 }  // namespace lgm

@@ -343,10 +343,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_F
     }
 #ifdef LGM_FWD_STAMPS
     if (d.counters && tid == 0) {
-        d.counters[8 + 8 * (size_t)tile + 2] = fs_head;  // (wave 0: termination count + staging + entry tests + barrier)
-        d.counters[8 + 8 * (size_t)tile + 3] = fs_mid;   // (checkpoint stores + compaction)
-        d.counters[8 + 8 * (size_t)tile + 4] = fs_comp;  // (the compositing loop)
-        d.counters[8 + 8 * (size_t)tile + 5] = sec_stamp() - fs_t0;  // (the whole chunk loop)
+        d.counters[cnt_tile(tile) + 2] = fs_head;  // (wave 0: termination count + staging + entry tests + barrier)
+        d.counters[cnt_tile(tile) + 3] = fs_mid;   // (checkpoint stores + compaction)
+        d.counters[cnt_tile(tile) + 4] = fs_comp;  // (the compositing loop)
+        d.counters[cnt_tile(tile) + 5] = sec_stamp() - fs_t0;  // (the whole chunk loop)
     }
 #endif
     if (zero_n16 > 0) {
@@ -374,10 +374,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_F
             // low half), the XCD (XCC_ID) in the top byte of [+7]
             const unsigned hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);
             const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);
-            d.counters[8 + 8 * (size_t)tile] = t_start;
-            d.counters[8 + 8 * (size_t)tile + 1] = __builtin_amdgcn_s_memrealtime();
-            d.counters[8 + 8 * (size_t)tile + 6] = (unsigned long long)(unsigned)n | ((unsigned long long)hw_id << 32);
-            d.counters[8 + 8 * (size_t)tile + 7] = (unsigned long long)c_list | ((unsigned long long)c_iter << 32) |
+            d.counters[cnt_tile(tile)] = t_start;
+            d.counters[cnt_tile(tile) + 1] = __builtin_amdgcn_s_memrealtime();
+            d.counters[cnt_tile(tile) + 6] = (unsigned long long)(unsigned)n | ((unsigned long long)hw_id << 32);
+            d.counters[cnt_tile(tile) + 7] = (unsigned long long)c_list | ((unsigned long long)c_iter << 32) |
                                                    ((unsigned long long)xcc << 56);
         }
     }
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(256) void k_det_seed_max(Dims d, const float *__res
 // entry and flushed once per (chunk, entry) to the per-view accumulators.
 // Occupancy: at least 4 waves per SIMD for the register allocation (<= 128 VGPRs; the 64-entry chunks' LDS admits 4
 // workgroups per CU); 2 for the depth-gradient instantiation, which LGM never runs.
-// AA: LGM_RENDER_ANTIALIAS -- the opacity partial is flushed per (view, Gaussian) (acc_aa_offset) instead of into the
+// AA: LGM_RENDER_ANTIALIAS -- the opacity partial is flushed per (view, Gaussian) (accum_aa_elem0) instead of into the
 // scene's record: k_preproc_bwd needs dL/do^ of each view. Compile-time, so the other instantiations are unchanged.
 template <bool DEPTH, bool LOSS, bool DET, bool AA = false>  // DET: LGM_RENDER_DETERMINISTIC (int64 fixed-point flush)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 : 4))) void k_render_bwd(
@@ -1159,8 +1159,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
             if (q < NV && j < CH && b0 + j < s1) {
                 const float a = o[q * LS + j];
                 const unsigned gid = sId[j];
-                size_t ai = acc_index(q, gbase + gid, (size_t)b * d.N + gid, (size_t)d.BV * d.N);
-                if (AA && q == 5) ai = acc_aa_offset(d.B, d.V, d.N, DET) + gbase + gid;  // per view, not per scene
+                // NACC order: mean2D 0..1 and conic 2..4 (per view), opacity 5 and colour 6..8 (per scene: ks is the
+                // scene record's first element), depth 9
+                const size_t k = gbase + gid, ks = accum_scene_elem(d.BV, d.N, b, gid, 0);
+                size_t ai = q < 5 ? accum_view_elem(k, q) : q < 9 ? ks + (q - 5) : accum_view_elem(k, 5);
+                if (AA && q == 5) ai = accum_aa_elem0(d.B, d.V, d.N, DET) + gbase + gid;  // per view, not per scene
                 if (a != 0.f) {
                     if (DET) {  // integer adds commute: order-independent sums (a is already in fixed-point units)
                         // (a per-view record takes at most T flushes, a per-scene one (q = 5..8) V * T: with |a|
@@ -1184,10 +1187,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
                 const float a = o[(NV + c3) * LS + j];
                 if (a != 0.f && b0 + j < s1) {
                     const unsigned gid = sId[j];
-                    // (the side block's offset recomputed here from the SGPR dims: a pointer hoisted out of the
+                    // (the needle block's offset recomputed here from the SGPR dims: a pointer hoisted out of the
                     // chunk loop was kept in VGPRs and spilled)
-                    const size_t so = acc_side_offset(d.B, d.V, d.N) / 2;
-                    atomicAdd(reinterpret_cast<double *>(accum) + so + (gbase + gid) * 3 + c3, (double)a);
+                    atomicAdd(reinterpret_cast<double *>(accum) + accum_needle_dbl(d.B, d.V, d.N, gbase + gid, c3),
+                              (double)a);
                 }
             }
         }
@@ -1203,7 +1206,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
         for (int q = 0; q < 8; q++) atomicAdd(&d.counters[q], sec[q]);
 #endif
     if (d.counters && tid == 0) {  // work-item timeline (lgm_diag.render_counters): start, end, (length | chunk | tile)
-        unsigned long long *o = d.counters + item_stamps + 4 * (size_t)blockIdx.x;
+        unsigned long long *o = d.counters + item_stamps + CNT_ITEM * (size_t)blockIdx.x;
         o[0] = t_item;
         o[1] = __builtin_amdgcn_s_memrealtime();
         o[2] = (unsigned long long)(s1 - s0) | ((unsigned long long)c << 20) | ((unsigned long long)tile << 40);
@@ -1276,15 +1279,15 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
     const bool det = (d.options & LGM_RENDER_DETERMINISTIC) != 0;
     const int det_s = det ? det_seed_shift(det_max) : 0;
     const bool det_bad = det && *det_sat != 0u;  // a fixed-point flush overflowed (k_render_bwd): poison the call
-    // LGM_RENDER_ANTIALIAS: the opacity partial arrives per view (G_v = dL/do^, acc_aa_offset), not per scene
+    // LGM_RENDER_ANTIALIAS: the opacity partial arrives per view (G_v = dL/do^, accum_aa_elem0), not per scene
     constexpr bool aa = AA;
-    const size_t aa_off = aa ? acc_aa_offset(d.B, d.V, d.N, det) : 0;
+    const size_t aa_off = aa ? accum_aa_elem0(d.B, d.V, d.N, det) : 0;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     // diagnostics: workgroup g's start / end in slots [2], [3] of per-tile record g (unused by the other kernels)
     const size_t g_diag = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     const bool stamp = d.counters && threadIdx.x == 0 && g_diag < (size_t)d.BV * d.T;
-    if (stamp) d.counters[8 + 8 * g_diag + 2] = __builtin_amdgcn_s_memrealtime();
+    if (stamp) d.counters[cnt_tile(g_diag) + 2] = __builtin_amdgcn_s_memrealtime();
     const bool live = i < d.N;
     const float fx = d.fx, fy = d.fy, mod = d.mod;
     // float mode: the accumulator row is loaded beside the rect, not after it (one memory round trip per view
@@ -1297,7 +1300,7 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
         const size_t k = ((size_t)b * d.V + v) * d.N + i;
         r_nx = rects[k];
         if (!det) {
-            const float2 *acc2 = reinterpret_cast<const float2 *>(accum + k * NACC_V);
+            const float2 *acc2 = reinterpret_cast<const float2 *>(accum + accum_view_elem(k, 0));
 #pragma unroll
             for (int q = 0; q < NACC_V / 2; q++) acc_nx[q] = acc2[q];
             if (aa) aa_nx = accum[aa_off + k];
@@ -1305,7 +1308,7 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
         if (aa) aa_snx = d.aa_s[k];  // (k_aa_factor: the forward's own s_v)
     };
     float g[14];
-    const size_t ks = (size_t)d.BV * d.N * NACC_V + ((size_t)b * d.N + i) * NACC_S;  // view-independent partials
+    const size_t ks = accum_scene_elem(d.BV, d.N, b, i, 0);  // view-independent partials
     float4 acc_s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (LDSV && live) {  // the Gaussian, its first view and its scene partials in flight during the staging
         load_gaussian(gauss + ((size_t)b * d.N + i) * 14, g);
@@ -1349,7 +1352,8 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
         }
         float acc[NACC_V];
         if (det) {  // back from fixed point: the same normalisers k_render_bwd derived from this record
-            const longlong2 *acc2 = reinterpret_cast<const longlong2 *>(accum) + k * (NACC_V / 2);
+            const longlong2 *acc2 = reinterpret_cast<const longlong2 *>(reinterpret_cast<const long long *>(accum) +
+                                                                        accum_view_elem(k, 0));
             const float4 rp = gP[k];
             const DetNorm nm = det_norm(rp.z, rp.w, gQ[k].x, d.W, d.H);
 #pragma unroll
@@ -1366,7 +1370,7 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
             }
         }
         if (!det && (r.y >> 31)) {  // a needle: its conic partials were summed in fp64
-            const double *sd = reinterpret_cast<const double *>(accum + acc_side_offset(d.B, d.V, d.N)) + k * 3;
+            const double *sd = reinterpret_cast<const double *>(accum) + accum_needle_dbl(d.B, d.V, d.N, k, 0);
             acc[2] = (float)sd[0];
             acc[3] = (float)sd[1];
             acc[4] = (float)sd[2];
@@ -1503,67 +1507,54 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
 #pragma unroll
     for (int kk = 0; kk < 7; kk++)
         o2[kk] = det_bad ? make_float2(qnan, qnan) : make_float2(out[2 * kk], out[2 * kk + 1]);
-    if (stamp) d.counters[8 + 8 * g_diag + 3] = __builtin_amdgcn_s_memrealtime();
+    if (stamp) d.counters[cnt_tile(g_diag) + 3] = __builtin_amdgcn_s_memrealtime();
 }
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------
 int launch_render_fwd(const Dims &d, const float *gaussians, const float *bg, float *image, float *depth,
-                      float *alpha, char *ws, const Layout &L, hipStream_t st) {
+                      float *alpha, const Workspace &w, const Layout &L, hipStream_t st) {
     const bool small = d.BV * d.T <= FWD_SMALL_TILES;
     auto fwd = (d.options & LGM_RENDER_FUSED_LOSS) ? (small ? k_render_fwd<true, 8> : k_render_fwd<true, FWD_FU>)
                                                    : (small ? k_render_fwd<false, 8> : k_render_fwd<false, FWD_FU>);
     LGM_LAUNCH("k_render_fwd", st, (fwd<<<(unsigned)(d.BV * d.T), 256, 0, st>>>(
-                                       d, L.slot ? (long long)d.N : -1LL, (const int *)(ws + L.tile_start),
-                                       (const int *)(ws + L.tile_count), (const unsigned long long *)(ws + L.pairs),
-                                       (const float4 *)(ws + L.gP), (const float4 *)(ws + L.gQ), gaussians, bg,
-                                       image, depth, alpha,
-                                       (float *)(ws + L.final_T), (int *)(ws + L.n_contrib), (int *)(ws + L.wlast),
-                                       (unsigned char *)(ws + L.cmask), (float4 *)(ws + L.cfin),
-                                       (float *)(ws + L.ck), (int2 *)(ws + L.cklist), (int *)(ws + L.nck),
-                                       (unsigned *)(ws + L.misc) + 4, L.ck_region, (float4 *)(ws + L.accum),
-                                       // (rounded up to 16 B: the tail lands in the layout's
-                                       // alignment padding, or on the fp64 side block's first entry, zeroed anyway)
-                                       (long long)(((d.options & LGM_RENDER_DETERMINISTIC ? 8 : 4) * acc_elems(d.B, d.V, d.N) + 15) / 16))));
+                                       d, L.slot ? (long long)d.N : -1LL, w.tile_start, w.tile_count, w.pairs, w.gP,
+                                       w.gQ, gaussians, bg, image, depth, alpha, w.final_T, w.n_contrib, w.wlast,
+                                       w.cmask, w.cfin, w.ck, w.cklist, w.nck, w.ck_counters, L.ck_region, w.accum16,
+                                       (long long)(L.acc.fwd_zero().bytes / 16))));
     return LGM_OK;
 }
 
-int launch_loss_reduce(const Dims &d, char *ws, const Layout &L, hipStream_t st) {
+int launch_loss_reduce(const Dims &d, const Workspace &w, hipStream_t st) {
     const double P = (double)d.H * d.W;
     const int M = d.BV * d.T, G = (M + LR_TILES - 1) / LR_TILES;
     LGM_LAUNCH("k_loss_reduce", st, (k_loss_reduce<<<G, LR_THREADS, 0, st>>>(
-                                        M, (const float2 *)(ws + L.lossp), 3.0 * d.BV * P, d.BV * P,
-                                        (double2 *)(ws + L.lossw), (unsigned *)(ws + L.misc) + 12, d.loss_out)));
+                                        M, w.lossp, 3.0 * d.BV * P, d.BV * P, w.lossw, w.loss_arrival, d.loss_out)));
     return LGM_OK;
 }
 
 int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
                       const float *bg, const float *d_image, const float *d_depth, const float *d_alpha,
-                      float *d_gaussians, float *d_means2D, char *ws, const Layout &L, hipStream_t st) {
-    // the accumulators were zeroed by the forward (k_render_fwd's epilogue); a repeated backward of the same forward
-    // clears what the previous one left
-    // (with LGM_RENDER_ANTIALIAS the per-view opacity partials, which end the block, included)
+                      float *d_gaussians, float *d_means2D, const Workspace &w, const Layout &L, hipStream_t st) {
+    // the accumulators were zeroed by the forward (AccumLayout: who zeroes what); a repeated backward of the same
+    // forward clears what the previous one left
     if ((d.options & LGM_RENDER_BACKWARD_AGAIN) &&
-        hipMemsetAsync(ws + L.accum, 0, acc_clear_bytes(d.B, d.V, d.N, (d.options & LGM_RENDER_DETERMINISTIC) != 0,
-                                                        (d.options & LGM_RENDER_ANTIALIAS) != 0),
-                       st) != hipSuccess) {
+        hipMemsetAsync(w.accum_range(L.acc.clear()), 0, L.acc.clear().bytes, st) != hipSuccess) {
         set_error("hipMemsetAsync failed");
         return LGM_E_HIP;
     }
     const bool loss = (d.options & LGM_RENDER_FUSED_LOSS) != 0, det = (d.options & LGM_RENDER_DETERMINISTIC) != 0;
-    unsigned *det_max = (unsigned *)(ws + L.detmax);
     if (det) {  // the call's fixed-point scale: max |dL/dpixel| over every seed (k_det_seed_max)
-        if (hipMemsetAsync(det_max, 0, DET_SLOTS * 4, st) != hipSuccess) {
+        if (hipMemsetAsync(w.detmax, 0, DET_SLOTS * 4, st) != hipSuccess) {
             set_error("hipMemsetAsync failed");
             return LGM_E_HIP;
         }
         auto smax = loss ? (d_depth ? k_det_seed_max<true, true> : k_det_seed_max<false, true>)
                          : (d_depth ? k_det_seed_max<true, false> : k_det_seed_max<false, false>);
         LGM_LAUNCH("k_det_seed_max", st, (smax<<<(unsigned)min(d.BV * d.T, DET_MAX_WGS), 256, 0, st>>>(
-                                             d, (const float *)(ws + L.final_T), bg, (const float4 *)(ws + L.cfin),
-                                             d_image, d_depth, d_alpha, (const unsigned char *)(ws + L.cmask),
-                                             det_max, (unsigned *)(ws + L.misc) + 13)));
+                                             d, w.final_T, bg, w.cfin, d_image, d_depth, d_alpha, w.cmask, w.detmax,
+                                             w.det_sat)));
     }
     const bool aa = (d.options & LGM_RENDER_ANTIALIAS) != 0;
     auto pick = [&](auto depth_tag) {
@@ -1578,26 +1569,16 @@ int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_vi
     // work items: chunk 0 of every tile, then one per checkpoint slot (unused slots exit at once)
     const int M = d.BV * d.T, Mp = round8(M);
     LGM_LAUNCH("k_render_bwd", st, (bwd<<<(unsigned)(Mp + L.ck_slots), 256, 0, st>>>(
-                                       d, L.slot ? (long long)d.N : -1LL, (const int *)(ws + L.tile_start),
-                                       (const int *)(ws + L.tile_count), (const unsigned long long *)(ws + L.pairs),
-                                       (const float4 *)(ws + L.gP), (const float4 *)(ws + L.gQ), gaussians, bg,
-                                       (const float *)(ws + L.final_T), (const int *)(ws + L.n_contrib),
-                                       (const int *)(ws + L.wlast), (const float4 *)(ws + L.cfin), (const float *)(ws + L.ck),
-                                       (const int2 *)(ws + L.cklist), (const int *)(ws + L.nck),
-                                       (const unsigned *)(ws + L.misc) + 4, L.ck_region, d_image, d_depth, d_alpha,
-                                       (const unsigned char *)(ws + L.cmask), (float *)(ws + L.accum), det_max,
-                                       (unsigned *)(ws + L.misc) + 13,
-                                       // (debug counters: after the per-tile and per-binning-workgroup records)
-                                       8 + 8LL * d.BV * d.T + 8LL * d.BV * ((d.N + 511) / 512))));
+                                       d, L.slot ? (long long)d.N : -1LL, w.tile_start, w.tile_count, w.pairs, w.gP,
+                                       w.gQ, gaussians, bg, w.final_T, w.n_contrib, w.wlast, w.cfin, w.ck, w.cklist,
+                                       w.nck, w.ck_counters, L.ck_region, d_image, d_depth, d_alpha, w.cmask, w.accum,
+                                       w.detmax, w.det_sat, (long long)cnt_item0(d.BV, d.T, d.N))));
     dim3 grid((d.N + 255) / 256, d.B);
     auto pre = aa ? (d.V <= PRE_MAXV ? k_preproc_bwd<true, true> : k_preproc_bwd<false, true>)
                   : (d.V <= PRE_MAXV ? k_preproc_bwd<true> : k_preproc_bwd<false>);
-    LGM_LAUNCH("k_preproc_bwd", st, (pre<<<grid, 256, 0, st>>>(d, gaussians, cam_view, cam_view_proj,
-                                                                        (const uint2 *)(ws + L.rects),
-                                                                        (float *)(ws + L.accum), d_gaussians,
-                                                                        d_means2D, (const float4 *)(ws + L.gP),
-                                                                        (const float4 *)(ws + L.gQ), det_max,
-                                                                        (const unsigned *)(ws + L.misc) + 13)));
+    LGM_LAUNCH("k_preproc_bwd", st, (pre<<<grid, 256, 0, st>>>(d, gaussians, cam_view, cam_view_proj, w.rects, w.accum,
+                                                               d_gaussians, d_means2D, w.gP, w.gQ, w.detmax,
+                                                               w.det_sat)));
     return LGM_OK;
 }
 

@@ -18,8 +18,7 @@ g = synthetic_gaussians(B, 100000, seed=1 if B == 1 else 2).to(dev).requires_gra
 cv, cvp, cp = (t[None].expand(B, *t.shape).contiguous().to(dev) for t in orbit_cameras(6))
 d_img, _, d_alpha, bg = synthetic_upstream_grads(B, 6, 256, 256, seed=1001 if B == 1 else 1002)
 L = _native.lib()
-M = B * 6 * 256
-cnt = torch.zeros(8 + 8 * M + 8 * B * 6 * 200 + 4 * 5 * M, dtype=torch.int64, device=dev)
+cnt = torch.zeros(_native.render_counter_words(B, 6, 100000, 256, 256), dtype=torch.int64, device=dev)
 for it in range(6):
     o = r.render(g, cv, cvp, cp, bg_color=bg.to(dev))
     torch.cuda.synchronize()

@@ -18,8 +18,8 @@ cv, cvp, cp = (t[None].expand(B, *t.shape).contiguous().to(dev) for t in orbit_c
 d_img, _, d_alpha, bg = synthetic_upstream_grads(B, 6, 256, 256, seed=1001 if B == 1 else 1002)
 M = B * 6 * 256
 NB = B * 6 * ((100000 + 511) // 512)  # binning records reserved (k_bin uses the first B*ceil(6/3)*ceil(N/512): 3 views per workgroup)
-NI = 12 * M + 256  # backward work-item capacity (the one-wave backward: 4 items per tile and per checkpoint slot)
-cnt = torch.zeros(8 + 8 * M + 8 * NB + 4 * NI, dtype=torch.int64, device=dev)
+NI = 3 * M + 16  # backward work-item records (include/lgm_render.h)
+cnt = torch.zeros(_native.render_counter_words(B, 6, 100000, 256, 256), dtype=torch.int64, device=dev)
 L = _native.lib()
 for _ in range(5):  # warm up (clocks, caches, code objects) before the instrumented step
     o = r.render(g, cv, cvp, cp, bg_color=bg.to(dev))

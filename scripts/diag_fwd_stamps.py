@@ -21,8 +21,7 @@ g = synthetic_gaussians(1, 50_000, seed=seed).to(dev)
 cv, cvp, cp = (t[None].to(dev) for t in orbit_cameras(1))
 bg = torch.ones(3, device=dev)
 M = 256
-NB = (50_000 + 511) // 512
-cnt = torch.zeros(8 + 8 * M + 8 * NB + 4 * 5 * M + 32 * M, dtype=torch.int64, device=dev)
+cnt = torch.zeros(_native.render_counter_words(1, 1, 50_000, 256, 256), dtype=torch.int64, device=dev)
 with torch.no_grad():
     for _ in range(5):
         r.render(g, cv, cvp, cp, bg_color=bg)

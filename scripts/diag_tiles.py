@@ -17,8 +17,7 @@ r = GaussianRenderer(Options(output_size=256))
 g = synthetic_gaussians(1, 100000, seed=1).to(dev)
 cv, cvp, cp = orbit_cameras(6)
 M = 6 * 256
-NB = 6 * ((100000 + 511) // 512)
-cnt = torch.zeros(8 + 8 * M + 8 * NB + 4 * 5 * M + 32 * M, dtype=torch.int64, device=dev)
+cnt = torch.zeros(_native.render_counter_words(1, 6, 100000, 256, 256), dtype=torch.int64, device=dev)
 L = _native.lib()
 r.render(g, cv[None].to(dev), cvp[None].to(dev), cp[None].to(dev))
 torch.cuda.synchronize()

@@ -24,7 +24,7 @@ d_img, d_alpha, bg = d_img.to(dev), d_alpha.to(dev), bg.to(dev)
 M = 6 * 256
 NB = 6 * ((100000 + 511) // 512)
 NI = 3 * M + 16
-cnt = torch.zeros(8 + 8 * M + 8 * NB + 4 * NI, dtype=torch.int64, device=dev)
+cnt = torch.zeros(_native.render_counter_words(1, 6, 100000, 256, 256), dtype=torch.int64, device=dev)
 for _ in range(200):  # clocks up
     o = r.render(g, cv, cvp, cp, bg_color=bg)
     torch.autograd.backward([o["image"], o["alpha"]], [d_img, d_alpha])

@@ -206,7 +206,7 @@ def test_stamps(cuda, small, small_ref):
     B, V, N, H, W = (SHAPE[k] for k in ("B", "V", "N", "H", "W"))
     M = B * V * 12
     nb_room, nwg = B * V * ((N + 511) // 512), B * ((V + 2) // 3) * ((N + 511) // 512)
-    cnt = torch.zeros(8 + 8 * M + 8 * nb_room + 4 * (3 * M + 16), dtype=torch.int64, device=cuda)  # lgm_render.h
+    cnt = torch.zeros(_native.render_counter_words(B, V, N, H, W), dtype=torch.int64, device=cuda)
     st = _forward(cuda, *small, H, W, stats=False, counters=cnt)
     _same(st, small_ref[False], "stamped vs unstamped")
     rec = cnt[8 + 8 * M:8 + 8 * M + 8 * nb_room].view(nb_room, 8).cpu().numpy()

@@ -440,10 +440,10 @@ def test_two_chunk_items_float_path_vs_oracle(cuda, oracle_mod):
 
 
 def test_deterministic_checkpoint_split_independent_of_batch(cuda):
-    """Deterministic mode on a scene whose tiles walk many chunks (72^2, long lists: the shared checkpoint pool
-    would run out): the split of each tile's walk into backward work items follows the tile's own checkpoint quota,
-    so scene 0's gradients are bitwise the same rendered alone and inside a batch of three (different work order,
-    different timing)."""
+    """Deterministic mode on a scene whose tiles walk many chunks (72^2, long lists). The mode takes no backward
+    checkpoints -- one work item per tile walks the whole list, so no split can depend on the launch's size or on
+    which tiles won a shared pool -- and its int64 sums commute: scene 0's gradients are bitwise the same rendered
+    alone and inside a batch of three (different work order, different timing), and the same again on a second run."""
     from lgm_amd.gs import rasterize
     g, cv, cvp = scene(B=3, N=7000, V=2, seed=6, elevation=-15.0)
     d_img, _, d_alpha, bg = upstream(3, 2, 72, 72, seed=8)
