@@ -13,6 +13,7 @@
  *
  * Conventions (all pointers are DEVICE pointers unless stated; all arrays dense, row-major, fp32):
  *   gaussians      [B,N,14]  pos(3) opacity(1) scale(3) rotation(4: w,x,y,z) rgb(3)   (core/gs.py:45-49)
+ *                  ([B,N,11 + 3K] with the LGM_RENDER_SH_MASK bits: spherical-harmonics coefficients in place of rgb)
  *   cam_view       [B,V,4,4] the transposed w2c exactly as core/gs.py:54 passes it (read column-major)
  *   cam_view_proj  [B,V,4,4] likewise (core/gs.py:55)
  *   bg             [3]
@@ -62,7 +63,8 @@ int lgm_render_forward(int B, int V, int N, int H, int W, const float *gaussians
                        int options, void *stream, const lgm_diag *diag);
 
 /* Backward of all B x V renders (replaces B*V calls of _C.rasterize_gaussians_backward plus the autograd sum
- * over views). d_image / d_depth / d_alpha may be NULL (treated as zero). Writes d_gaussians [B,N,14] (overwrites).
+ * over views). d_image / d_depth / d_alpha may be NULL (treated as zero). Writes d_gaussians [B,N,14] (overwrites;
+ * the width of gaussians with the LGM_RENDER_SH_MASK bits).
  * d_means2D [B,V,N,2] (screen-space gradients, what upstream returns for means2D) may be NULL. */
 int lgm_render_backward(int B, int V, int N, int H, int W, const float *gaussians, const float *cam_view,
                         const float *cam_view_proj, const float *bg, float tanfovx, float tanfovy,
@@ -198,6 +200,44 @@ size_t lgm_render_workspace_size_opts(int B, int V, int N, int H, int W, long lo
  * (the early-out, tau, the candidate rect, the tile tests) is monotone in the opacity -- the antialiased forward's
  * own stats_out[0] is at most that count. */
 #define LGM_RENDER_ANTIALIAS 32
+
+/* LGM_RENDER_SH_MASK: view-dependent colour from spherical harmonics (the 3DGS rasteriser's shs / sh_degree / campos
+ * inputs). The degree is d = (options >> LGM_RENDER_SH_SHIFT) & 3. d = 0 is the plain RGB path: with the bits clear,
+ * not one operation or operand changes. For d in 1..3, K = (d + 1)^2 and
+ *   gaussians and d_gaussians are [B,N,11 + 3K]: columns 0:11 as ever, coefficient k of channel c at column
+ *   11 + 3k + c (the 3DGS shs [N,K,3] order, DC first).
+ * Colour, per (view v, Gaussian) with p the position:
+ *   campos_v = -t M^-1, the point cam_view_v sends to the origin (M = cam_view[:3,:3], t = cam_view[3,:3] in the
+ *   row-vector convention above; the inverse is taken in fp64, once per view and workgroup),
+ *   dir = (p - campos_v) / |p - campos_v| = (x, y, z),   colour_c = max(0, 1/2 + sum_k Y_k(dir) sh[k][c]),
+ * with the 3DGS rasteriser's real basis, signs and fp32 constants:
+ *   C0 = 0.28209479177387814, C1 = 0.4886025119029199,
+ *   C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396),
+ *   C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
+ *         1.445305721320277, -0.5900435899266435),
+ *   Y_0 = C0;  Y_1..3 = -C1 y, C1 z, -C1 x;
+ *   Y_4..8 = C2[0] xy, C2[1] yz, C2[2] (2zz - xx - yy), C2[3] xz, C2[4] (xx - yy);
+ *   Y_9..15 = C3[0] y (3xx - yy), C3[1] xyz, C3[2] y (4zz - xx - yy), C3[3] z (2zz - 3xx - 3yy),
+ *             C3[4] x (4zz - xx - yy), C3[5] z (xx - yy), C3[6] x (xx - 3yy).
+ * A record the preprocess cuts in a view (view depth <= 0.2, zero radius, an empty tile rect ...) gets no colour and
+ * no gradient from that view.
+ * Backward: with G_vc the compositing backward's colour partial of view v and m_vc = 1 where the unclamped colour is
+ * positive (else 0; upstream's `clamped`),
+ *   dL/dsh[k][c] = sum_v Y_k(dir_v) m_vc G_vc,
+ *   dL/dp += sum_v J_v^T g_v,  g_v = sum_c m_vc G_vc d(colour_c)/d(dir),  J_v the Jacobian of the normalisation,
+ * added to the mean gradient the projection produces. No gradient reaches the cameras. The sums over views and
+ * coefficients run in a fixed order, one writer per Gaussian, without float atomics in either accumulator mode.
+ * The workspace is larger (per-view colours, clamp masks and colour partials -- fp32, or int64 fixed point with the
+ * per-view bound lgm_render_det_flush_limit_log2(views, tiles, 0) in deterministic mode -- and 14-wide copies of the
+ * rows for the kernels that know no other width): size it with lgm_render_workspace_size_opts(..., options). A
+ * workspace sized without the bits is too short and returns LGM_E_WORKSPACE with nothing launched. Without the bits
+ * the workspace is byte for byte what it was. Pass the bits to forward and backward alike; they combine with every
+ * other option, the loss-fused pair and packed mode.
+ * lgm_render_count_pairs takes no options and reads 14-wide rows: hand it a contiguous [B,N,14] copy of columns 0:14
+ * (only 0:11 are read; colour does not enter the binning, so its counts hold for every degree). The inspection entry
+ * points read regions that the bits do not move. */
+#define LGM_RENDER_SH_SHIFT 6
+#define LGM_RENDER_SH_MASK (3 << 6)
 
 #ifdef __cplusplus
 }

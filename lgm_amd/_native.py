@@ -139,6 +139,8 @@ RENDER_CLAMP_IMAGE = 2  # include/lgm_render.h LGM_RENDER_CLAMP_IMAGE
 RENDER_BACKWARD_AGAIN = 4  # include/lgm_render.h LGM_RENDER_BACKWARD_AGAIN
 RENDER_DETERMINISTIC = 16  # include/lgm_render.h LGM_RENDER_DETERMINISTIC
 RENDER_ANTIALIAS = 32  # include/lgm_render.h LGM_RENDER_ANTIALIAS
+RENDER_SH_SHIFT = 6  # include/lgm_render.h LGM_RENDER_SH_SHIFT: the SH degree is (options >> 6) & 3
+RENDER_SH_MASK = 3 << 6  # include/lgm_render.h LGM_RENDER_SH_MASK
 DATA_U8 = 3  # include/lgm_data.h LGM_DATA_U8
 OPTIM_CHUNK = 4096  # include/lgm_optim.h LGM_OPTIM_CHUNK
 

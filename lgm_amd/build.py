@@ -8,7 +8,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/common.hip", "csrc/render_bin.hip", "csrc/render_raster.hip", "csrc/render_api.hip",
+SOURCES = ["csrc/common.hip", "csrc/render_bin.hip", "csrc/render_raster.hip", "csrc/render_sh.hip",
+           "csrc/render_api.hip",
            "csrc/attention.hip", "csrc/head.hip", "csrc/mvattn.hip", "csrc/wgrad.hip", "csrc/gnsilu.hip",
            "csrc/lpips.hip", "csrc/data.hip", "csrc/optim.hip", "csrc/conv_wgrad.hip",
            "csrc/conv_fwd.hip", "csrc/mesh.hip", "csrc/meshraster.hip"]

@@ -165,14 +165,24 @@ def render_cpu(gaussians, cam_view, cam_view_proj, bg, tanx, tany, H, W, scale_m
                antialias=False):
     """[B,N,14] CPU Gaussians -> (image [B,V,3,H,W], depth [B,V,1,H,W], alpha [B,V,1,H,W]); image clamped to
     [0, 1] when clamp (core/gs.py:87). antialias: the opacity compensation of LGM_RENDER_ANTIALIAS
-    (include/lgm_render.h), differentiated by autograd like the rest."""
+    (include/lgm_render.h), differentiated by autograd like the rest. Rows of 23 / 38 / 59 columns carry
+    spherical-harmonics coefficients (LGM_RENDER_SH_MASK): each view composites the colours lgm_amd.sh.eval_sh gives
+    for the directions from its camera position (derived from cam_view)."""
+    from . import sh as shm
     g_all = gaussians.float()
+    degree = shm.degree_of(g_all.shape[-1])
+    campos = shm.cam_positions(cam_view).float() if degree else None
     B, V = cam_view.shape[0], cam_view.shape[1]
     bgv = torch.as_tensor(bg, dtype=torch.float32).reshape(3)
     imgs, deps, alps = [], [], []
     for b in range(B):
-        g = g_all[b]
+        g_row = g_all[b]
         for v in range(V):
+            g = g_row
+            if degree:  # this view's colours in place of the RGB columns
+                dirs = torch.nn.functional.normalize(g_row[:, 0:3] - campos[b, v], dim=-1, eps=0.0)
+                g = torch.cat([g_row[:, :11], shm.eval_sh(degree, g_row[:, 11:].reshape(-1, shm.num_coeffs(degree), 3),
+                                                           dirs)], dim=-1)
             pre = _preprocess(g, cam_view[b, v].float(), cam_view_proj[b, v].float(), tanx, tany, H, W,
                               float(scale_modifier), antialias)
             start, lst = _tile_lists(pre)

@@ -40,6 +40,8 @@ int check_common(int B, int V, int N, int H, int W, const void *g, const void *c
     d.loss_part = d.loss_out = nullptr;
     d.d_loss = nullptr;
     d.aa_s = nullptr;
+    d.sh_col = nullptr;
+    d.sh_part = nullptr;
     return LGM_OK;
 }
 
@@ -102,6 +104,8 @@ int setup_call(lgm::Dims &d, int options, const lgm::Workspace &w, const float *
                const void *third, const char *pass, const char *third_name) {
     d.options = options & ~LGM_RENDER_FUSED_LOSS;
     d.aa_s = w.aa_s;
+    d.sh_col = w.sh_col;
+    d.sh_part = w.sh_part;
     if (gt_images || gt_masks || third) {
         if (!gt_images || !gt_masks || !third) {
             lgm::set_error("fused loss%s needs gt_images, gt_masks and %s", pass, third_name);
@@ -183,9 +187,15 @@ static int forward_impl(int B, int V, int N, int H, int W, const float *gaussian
         d.loss_out = loss_out;
     }
     hipStream_t st = (hipStream_t)stream;
-    rc = lgm::launch_binning(d, gaussians, cam_view, cam_view_proj, w, L, radii_out, stats_out, false, st);
+    // LGM_RENDER_SH_MASK: `gaussians` has rows of 11 + 3K; the kernels that know 14-wide rows run on the workspace's
+    // copy of columns 0:14, and the compositing stages the colours k_sh_colour wrote (render_sh.hip)
+    const int sh = N > 0 ? lgm::sh_degree_of(options) : 0;
+    if (sh && (rc = lgm::launch_sh_pack(d, sh, gaussians, w, L, st))) return rc;
+    const float *g14 = sh ? w.sh_g14 : gaussians;
+    rc = lgm::launch_binning(d, g14, cam_view, cam_view_proj, w, L, radii_out, stats_out, false, st);
     if (rc) return rc;
-    rc = lgm::launch_render_fwd(d, gaussians, bg, image, depth, alpha, w, L, st);
+    if (sh && (rc = lgm::launch_sh_colour(d, sh, gaussians, cam_view, w, st))) return rc;
+    rc = lgm::launch_render_fwd(d, g14, bg, image, depth, alpha, w, L, st);
     if (rc || !(d.options & LGM_RENDER_FUSED_LOSS)) return rc;
     return lgm::launch_loss_reduce(d, w, st);
 }
@@ -215,8 +225,12 @@ static int backward_impl(int B, int V, int N, int H, int W, const float *gaussia
     rc = setup_call(d, options, w, gt_images, gt_masks, d_loss, " backward", "d_loss");
     if (rc) return rc;
     d.d_loss = d_loss;
-    return lgm::launch_render_bwd(d, gaussians, cam_view, cam_view_proj, bg, d_image, d_depth, d_alpha, d_gaussians,
-                                  d_means2D, w, L, (hipStream_t)stream);
+    // LGM_RENDER_SH_MASK: k_preproc_bwd writes 14-wide rows to the workspace; k_sh_bwd then writes the caller's
+    const int sh = lgm::sh_degree_of(options);
+    rc = lgm::launch_render_bwd(d, sh ? w.sh_g14 : gaussians, cam_view, cam_view_proj, bg, d_image, d_depth, d_alpha,
+                                sh ? w.sh_dg14 : d_gaussians, d_means2D, w, L, (hipStream_t)stream);
+    if (rc || !sh) return rc;
+    return lgm::launch_sh_bwd(d, sh, gaussians, cam_view, d_gaussians, w, (hipStream_t)stream);
 }
 
 extern "C" {

@@ -35,7 +35,7 @@ struct Dims {
     unsigned long long *counters;  // this call's device work counters (lgm_diag.render_counters), or null
     int det_lim_log2;              // lgm_diag.det_limit_log2 (test hook; 0 = the derived bound)
     int options;                   // per-call LGM_RENDER_* bits (NO_CULL, CLAMP_IMAGE, FUSED_LOSS, DETERMINISTIC,
-                                   // ANTIALIAS)
+                                   // ANTIALIAS, the SH degree)
     int ck_shift;                  // backward work items span 2^ck_shift forward chunks (ck_shift_for(BV * T))
     // LGM_RENDER_FUSED_LOSS (core/models.py:138-160): ground truth [BV,3,P] / [BV,P], the per-tile loss partials
     // (forward) and the gradients of the two MSE terms (backward)
@@ -46,6 +46,10 @@ struct Dims {
     // LGM_RENDER_ANTIALIAS: the workspace's opacity factors s [BV, N] (Workspace::aa_s; k_aa_factor writes them ahead
     // of the binning), else null
     const float *aa_s;
+    // LGM_RENDER_SH_MASK: the workspace's per-view colours [BV, N, 3] (AccumLayout::sh_col) and colour partials
+    // [BV, N, 3] (AccumLayout::sh_part; fp32 or int64), else null
+    const float *sh_col;
+    void *sh_part;
 };
 
 // The workspace as typed pointers, built once per call: the one place that casts into it. (The kernels take the
@@ -71,6 +75,10 @@ struct Workspace {
     unsigned long long *pair_counts;                  // misc: MISC_PAIRS
     unsigned *ck_counters, *loss_arrival, *det_sat;  // misc: MISC_CK_REGION, MISC_LOSS_ARRIVAL, MISC_DET_SAT
     float *aa_s;  // LGM_RENDER_ANTIALIAS: the factors (AccumLayout::aa_s), else null
+    // LGM_RENDER_SH_MASK: AccumLayout::sh_col, sh_part, sh_mask, sh_g14, sh_dg14, else null
+    float *sh_col, *sh_g14, *sh_dg14;
+    void *sh_part;
+    unsigned char *sh_mask;
     Workspace(char *ws, const Layout &L) : base(ws) {
         auto at = [ws](auto *&p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(ws + off); };
         at(gP, L.gP); at(gQ, L.gQ); at(rects, L.rects);
@@ -83,6 +91,14 @@ struct Workspace {
         at(loss_arrival, L.misc + MISC_LOSS_ARRIVAL * 4); at(det_sat, L.misc + MISC_DET_SAT * 4);
         aa_s = nullptr;
         if (L.acc.aa_s.bytes) at(aa_s, L.accum + L.acc.aa_s.off);
+        sh_col = sh_g14 = sh_dg14 = nullptr;
+        sh_part = nullptr;
+        sh_mask = nullptr;
+        if (L.acc.sh_g14.bytes) {
+            at(sh_part, L.accum + L.acc.sh_part.off); at(sh_col, L.accum + L.acc.sh_col.off);
+            at(sh_mask, L.accum + L.acc.sh_mask.off); at(sh_g14, L.accum + L.acc.sh_g14.off);
+            at(sh_dg14, L.accum + L.acc.sh_dg14.off);
+        }
     }
     char *range(const Region &r) const { return base + r.off; }  // a range of the workspace (Layout::bin_clear)
     char *accum_range(const Region &r) const { return reinterpret_cast<char *>(accum) + r.off; }  // of AccumLayout
@@ -368,6 +384,22 @@ __device__ __forceinline__ void load_gaussian(const float *__restrict__ src, flo
     }
 }
 
+// Deterministic mode's per-call scale (render_raster.hip, "Deterministic mode", explains the units).
+constexpr int DET_BITS = 30;  // seed max -> 2^30 units: per flush |value| <= ~2^51, sums of 2^11 flushes < 2^63
+__device__ __forceinline__ int f32_exp(float x) { return (int)((__float_as_uint(x) >> 23) & 0xffu) - 127; }
+constexpr int DET_SLOTS = 64;  // k_det_seed_max spreads its atomics over this many words (same-address atomics serialise)
+__device__ __forceinline__ int det_seed_shift(const unsigned *det_max) {  // s: the call's global scale exponent
+    const uint4 *p = reinterpret_cast<const uint4 *>(det_max);
+    unsigned mb = 0u;
+#pragma unroll
+    for (int i = 0; i < DET_SLOTS / 4; i++) {
+        const uint4 v = p[i];
+        mb = max(max(mb, max(v.x, v.y)), max(v.z, v.w));
+    }
+    const float m = __uint_as_float(mb);
+    return (m > 0.f && m < 3.0e38f) ? DET_BITS - f32_exp(m) : 0;
+}
+
 // Tile bucket of one (view, tile): base offset into `pairs` and entry count.
 // slot_stride < 0 selects packed mode; slot mode uses stride N (possibly 0: then every bucket is empty).
 __device__ __forceinline__ void tile_range(int tile, long long slot_stride, const int *__restrict__ tile_start,
@@ -404,5 +436,13 @@ int launch_loss_reduce(const Dims &d, const Workspace &w, hipStream_t st);
 int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
                       const float *bg, const float *d_image, const float *d_depth, const float *d_alpha,
                       float *d_gaussians, float *d_means2D, const Workspace &w, const Layout &L, hipStream_t st);
+// LGM_RENDER_SH_MASK (render_sh.hip): `wide` / `d_wide` are the caller's [B,N,11+3K] rows. launch_sh_pack runs ahead
+// of the binning (the 14-wide copy, the colour partials' zeroing), launch_sh_colour between the binning and
+// launch_render_fwd, launch_sh_bwd after launch_render_bwd.
+int launch_sh_pack(const Dims &d, int degree, const float *wide, const Workspace &w, const Layout &L, hipStream_t st);
+int launch_sh_colour(const Dims &d, int degree, const float *wide, const float *cam_view, const Workspace &w,
+                     hipStream_t st);
+int launch_sh_bwd(const Dims &d, int degree, const float *wide, const float *cam_view, float *d_wide,
+                  const Workspace &w, hipStream_t st);
 
 }  // namespace lgm

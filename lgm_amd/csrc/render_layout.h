@@ -51,9 +51,25 @@ struct Region {  // bytes [off, off + bytes)
 //   aa_part a memset in launch_binning, every forward with the bit.
 //   all three again: launch_render_bwd's memset of clear() under LGM_RENDER_BACKWARD_AGAIN, which clears what the
 //           previous backward of the same forward left. The factors stay.
+// Spherical harmonics (the LGM_RENDER_SH_MASK bits, degree 1..3: lgm_render.h) append five more regions, each 16-B
+// aligned; without the bits they are empty and the block is byte for byte what it was:
+//   sh_part the colour partials per (view, Gaussian) instead of per scene, 3 elements each (fp32, or int64 with the
+//           per-view flush bound in deterministic mode): the SH backward needs G_v = dL/dcolour of each view. The
+//           scene records' colour elements are then never added to (they stay zero). Zeroed by a memset in
+//           launch_sh_pack, every forward with the bits, and again by launch_render_bwd's memset of sh_part under
+//           LGM_RENDER_BACKWARD_AGAIN.
+//   sh_col  the colours the basis gives, fp32 [B, V, N, 3]: k_sh_colour writes the visible records' after the
+//           binning, k_render_fwd and k_render_bwd stage them in place of the row's RGB. An invisible record's is
+//           never written nor read (it is in no tile list). Not an accumulator.
+//   sh_mask one byte per (view, Gaussian), bit c = channel c's unclamped colour is positive (upstream's `clamped`,
+//           inverted). Written beside sh_col, read by k_sh_bwd. Not an accumulator.
+//   sh_g14  [B, N, 14] fp32: columns 0:14 of the caller's wider rows, copied by k_sh_pack ahead of the binning, so
+//           that every kernel written for 14-wide rows (k_bin, k_aa_factor, k_preproc_bwd) runs unchanged on them.
+//   sh_dg14 [B, N, 14] fp32: what k_preproc_bwd writes as d_gaussians; k_sh_bwd then writes the caller's wide rows
+//           from its columns 0:11, the position term and dL/dsh. Overwritten by every backward, never accumulated.
 struct AccumLayout {
     int elem;  // bytes per accumulator element: 4 (fp32), 8 (int64, deterministic mode)
-    Region main, needle, aa_part, aa_s;
+    Region main, needle, aa_part, aa_s, sh_part, sh_col, sh_mask, sh_g14, sh_dg14;
     size_t total;
     LGM_HD Region clear() const { return {0, aa_s.off}; }  // every accumulator (and the padding between them)
     LGM_HD Region fwd_zero() const { return {0, (main.bytes + 15) / 16 * 16}; }
@@ -66,7 +82,7 @@ LGM_HD size_t accum_needle_elem0(size_t B, size_t V, size_t N) { return (accum_m
 LGM_HD size_t accum_needle_elem1(size_t B, size_t V, size_t N) {
     return accum_needle_elem0(B, V, N) + B * V * N * (NEEDLE_DBL * sizeof(double) / sizeof(float));
 }
-LGM_HD AccumLayout accum_layout(size_t B, size_t V, size_t N, bool det, bool aa) {
+LGM_HD AccumLayout accum_layout(size_t B, size_t V, size_t N, bool det, bool aa, int sh_degree = 0) {
     AccumLayout a;
     a.elem = det ? 8 : 4;
     a.main = {0, accum_main_elems(B, V, N) * a.elem};
@@ -75,8 +91,22 @@ LGM_HD AccumLayout accum_layout(size_t B, size_t V, size_t N, bool det, bool aa)
     a.aa_part = {a.needle.end(), aa ? B * V * N * a.elem : 0};
     a.aa_s = {a.aa_part.end(), aa ? B * V * N * sizeof(float) : 0};
     a.total = a.aa_s.end();
+    const size_t sh = sh_degree > 0 ? 1 : 0;
+    auto next = [&](size_t bytes) {  // (16-B aligned; an empty region sits where the block ended)
+        const Region r{sh ? (a.total + 15) / 16 * 16 : a.total, sh * bytes};
+        a.total = r.end();
+        return r;
+    };
+    a.sh_part = next(B * V * N * 3 * a.elem);
+    a.sh_col = next(B * V * N * 3 * sizeof(float));
+    a.sh_mask = next(B * V * N);
+    a.sh_g14 = next(B * N * 14 * sizeof(float));
+    a.sh_dg14 = next(B * N * 14 * sizeof(float));
     return a;
 }
+// the SH degree of a call's options (0: plain RGB rows) and the row width it implies
+LGM_HD int sh_degree_of(int options) { return (options & LGM_RENDER_SH_MASK) >> LGM_RENDER_SH_SHIFT; }
+LGM_HD int sh_row_width(int degree) { return degree > 0 ? 11 + 3 * (degree + 1) * (degree + 1) : 14; }
 // Device code keeps no AccumLayout live across its hot loops (hoisted addresses spilled in k_render_bwd): it calls
 // these at the point of use. Indices into the block as an array of its elements (fp32 / int64), or of doubles.
 // k = (b V + v) N + i: the (view, Gaussian) record; (b, i): the (scene, Gaussian) record; BV = B V.
@@ -178,6 +208,7 @@ struct Layout {
 // deterministic k_render_bwd 1950 / 1306 / 955 / 787 / 685 / 650 us at quota 16 / 8 / 4 / 2 / 1 / 0 (float mode
 // 626) -- in the fixed-point mode the split costs more than its load balance returns.
 // LGM_RENDER_ANTIALIAS: the accumulator block carries the per-view opacity partials and the factors (AccumLayout).
+// LGM_RENDER_SH_MASK: it carries the per-view colours, masks and colour partials and the 14-wide row copies.
 inline Layout make_layout(int B, int V, int N, int H, int W, long long pair_capacity, int options) {
     const bool det = (options & LGM_RENDER_DETERMINISTIC) != 0, aa = (options & LGM_RENDER_ANTIALIAS) != 0;
     const size_t BV = (size_t)B * V, T = (size_t)((W + BX - 1) / BX) * ((H + BY - 1) / BY), P = (size_t)H * W;
@@ -212,7 +243,7 @@ inline Layout make_layout(int B, int V, int N, int H, int W, long long pair_capa
     L.cklist = take((size_t)L.ck_slots * 8);
     L.nck = take(BV * T * 4);
     L.cmask = take(BV * P);
-    L.acc = accum_layout(B, V, N, det, aa);
+    L.acc = accum_layout(B, V, N, det, aa, sh_degree_of(options));
     L.accum = take(L.acc.total);
     L.lossp = take(BV * T * 2 * 4);  // per-tile sums of squared image / alpha residuals (fused loss)
     L.lossw = take(((BV * T + 2047) / 2048) * 16);  // their per-workgroup double2 partials (k_loss_reduce)

@@ -94,7 +94,9 @@ using StageBwd = StageT<2, MB, BWD_CHUNK>;
 
 // Issue the LDS DMA of one entry (this lane's row of wave w's 64-row slice; lds_dma, cdna4.h). Asynchronous: the
 // rows are valid after vm_wait() in every issuing wave followed by a barrier.
-template <class Buf>
+// SH (LGM_RENDER_SH_MASK): the colour comes from the view's own record in `gauss` = Dims::sh_col [BV, N, 3] (12-B
+// stride, 4-B aligned like the row's RGB) instead of the scene's 14-wide row.
+template <bool SH = false, class Buf>
 __device__ __forceinline__ void stage_dma(Buf &B, int w, unsigned gid, size_t gbase, int b, int N,
                                           const float4 *__restrict__ gP, const float4 *__restrict__ gQ,
                                           const float *__restrict__ gauss) {
@@ -102,7 +104,8 @@ __device__ __forceinline__ void stage_dma(Buf &B, int w, unsigned gid, size_t gb
     const unsigned base = lds_offset(&B) + (unsigned)(w * 64 * 16);
     lds_dma<16>(gP + gbase + gid, base + (unsigned)offsetof(Buf, P));
     lds_dma<16>(gQ + gbase + gid, base + (unsigned)offsetof(Buf, Q));
-    lds_dma<12>(gauss + ((size_t)b * N + gid) * 14 + 11, base + (unsigned)offsetof(Buf, R));
+    if constexpr (SH) lds_dma<12>(gauss + (gbase + gid) * 3, base + (unsigned)offsetof(Buf, R));
+    else lds_dma<12>(gauss + ((size_t)b * N + gid) * 14 + 11, base + (unsigned)offsetof(Buf, R));
 }
 
 // Entry j of a landed chunk: its quadrant mask (the alpha >= 1/255 ellipse against the four 8x8 quadrants) and,
@@ -177,7 +180,9 @@ __device__ __forceinline__ void init_sentinel(Stage &S) {
 // (FWD_SMALL_TILES: a single 256^2 view, BASELINE config 2) run one wave per SIMD, where nothing hides a wave's own
 // dependency chains, and take FU = 8 at 2 waves per SIMD (more registers: twice the independent evaluations in flight).
 // The serial T / colour chain is in list order either way: the outputs are bitwise the same.
-template <bool LOSS, int FU>  // LOSS: LGM_RENDER_FUSED_LOSS compiled in (its epilogue registers stay out otherwise)
+// SH: LGM_RENDER_SH_MASK -- `gauss` is the per-view colour buffer (stage_dma). Compile-time, so the plain
+// instantiations are the code they were.
+template <bool LOSS, int FU, bool SH = false>  // LOSS: LGM_RENDER_FUSED_LOSS compiled in (its epilogue registers stay out otherwise)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_FU ? 7 : 2))) void k_render_fwd(Dims d, long long slot_stride,
                                                     const int *__restrict__ tile_start,
                                                     const int *__restrict__ tile_count,
@@ -241,7 +246,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_F
         c_list += min(TILE_PIX, n - b0);
         const int k = b0 + tid;
         StageBuf &B = S.buf[0];
-        if (k < n) stage_dma(B, w, id_a, gbase, b, d.N, gP, gQ, gauss);
+        if (k < n) stage_dma<SH>(B, w, id_a, gbase, b, d.N, gP, gQ, gauss);
         vm_wait();
         stage_commit(S, B, tid, k < n, 0u, tx0, ty0, false);
         __syncthreads();
@@ -579,20 +584,7 @@ __device__ __forceinline__ void pixel_seed(const Dims &d, bool inside, int bv, s
 //    |dL/dG|, so a large, elongated Gaussian's conic partials (pixel offsets of hundreds) cannot overflow int64 and a
 //    small one's keep their resolution.
 // Every power-of-two scaling is exact, so the only rounding is each flush's conversion to an integer (nearest).
-constexpr int DET_BITS = 30;  // seed max -> 2^30 units: per flush |value| <= ~2^51, sums of 2^11 flushes < 2^63
-__device__ __forceinline__ int f32_exp(float x) { return (int)((__float_as_uint(x) >> 23) & 0xffu) - 127; }
-constexpr int DET_SLOTS = 64;  // k_det_seed_max spreads its atomics over this many words (same-address atomics serialise)
-__device__ __forceinline__ int det_seed_shift(const unsigned *det_max) {  // s: the call's global scale exponent
-    const uint4 *p = reinterpret_cast<const uint4 *>(det_max);
-    unsigned mb = 0u;
-#pragma unroll
-    for (int i = 0; i < DET_SLOTS / 4; i++) {
-        const uint4 v = p[i];
-        mb = max(max(mb, max(v.x, v.y)), max(v.z, v.w));
-    }
-    const float m = __uint_as_float(mb);
-    return (m > 0.f && m < 3.0e38f) ? DET_BITS - f32_exp(m) : 0;
-}
+// (DET_BITS, DET_SLOTS and det_seed_shift, the per-call scale: render_common.h -- the SH backward decodes with it too)
 struct DetNorm {
     int k[6];  // exponents of the view record's slots: mean2D x, y, conic A, B, C, depth
 };
@@ -685,7 +677,10 @@ __global__ __launch_bounds__(256) void k_det_seed_max(Dims d, const float *__res
 // workgroups per CU); 2 for the depth-gradient instantiation, which LGM never runs.
 // AA: LGM_RENDER_ANTIALIAS -- the opacity partial is flushed per (view, Gaussian) (accum_aa_elem0) instead of into the
 // scene's record: k_preproc_bwd needs dL/do^ of each view. Compile-time, so the other instantiations are unchanged.
-template <bool DEPTH, bool LOSS, bool DET, bool AA = false>  // DET: LGM_RENDER_DETERMINISTIC (int64 fixed-point flush)
+// SH: LGM_RENDER_SH_MASK -- `gauss` is the per-view colour buffer (stage_dma) and the colour partials are flushed per
+// (view, Gaussian) to Dims::sh_part (k_sh_bwd needs dL/dcolour of each view), with the per-view flush bound.
+// Compile-time likewise.
+template <bool DEPTH, bool LOSS, bool DET, bool AA = false, bool SH = false>  // DET: LGM_RENDER_DETERMINISTIC (int64 fixed-point flush)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 : 4))) void k_render_bwd(
     Dims d, long long slot_stride, const int *__restrict__ tile_start,
     const int *__restrict__ tile_count, const unsigned long long *__restrict__ pairs, const float4 *__restrict__ gP,
@@ -758,7 +753,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
                                  // slower: pool k_render_bwd 608 -> 620 us, profiles/r06/ab_bwd_w3)
     const int s0e = (c * TILE_PIX) << d.ck_shift;
     unsigned id_cur = stager && s0e + lane < n ? ids[s0e + lane] : 0u;
-    if (stager && s0e + lane < n) stage_dma(S.buf[0], 0, id_cur, (size_t)bv * d.N, b, d.N, gP, gQ, gauss);
+    if (stager && s0e + lane < n) stage_dma<SH>(S.buf[0], 0, id_cur, (size_t)bv * d.N, b, d.N, gP, gQ, gauss);
     unsigned id_next = stager && s0e + BWD_CHUNK + lane < n ? ids[s0e + BWD_CHUNK + lane] : 0u;
     const size_t P = (size_t)d.H * d.W;
     const size_t pid = inside ? (size_t)d.W * py + px : 0;
@@ -979,7 +974,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
             constexpr int PAD = (int)(sizeof(S.list[0]) / sizeof(S.list[0][0])) - CH;
             if (lane < PAD) S.list[w][cnt + lane] = (unsigned short)CH;
         }
-        if (stager && b0 + lane + CH < s1) stage_dma(S.buf[cur ^ 1], 0, id_next, gbase, b, d.N, gP, gQ, gauss);
+        if (stager && b0 + lane + CH < s1) stage_dma<SH>(S.buf[cur ^ 1], 0, id_next, gbase, b, d.N, gP, gQ, gauss);
         id_cur = id_next;
         id_next = stager && b0 + lane + 2 * CH < s1 ? ids[b0 + lane + 2 * CH] : 0u;
         static_assert(MB == 8, "one batch = two 4-entry list words");
@@ -1164,17 +1159,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
                 const size_t k = gbase + gid, ks = accum_scene_elem(d.BV, d.N, b, gid, 0);
                 size_t ai = q < 5 ? accum_view_elem(k, q) : q < 9 ? ks + (q - 5) : accum_view_elem(k, 5);
                 if (AA && q == 5) ai = accum_aa_elem0(d.B, d.V, d.N, DET) + gbase + gid;  // per view, not per scene
+                // (SH) the colour partials go to the view's own record in Dims::sh_part, outside `accum`'s main region
+                const bool shq = SH && q >= 6 && q < 9;
+                if (shq) ai = (gbase + gid) * 3 + (q - 6);
                 if (a != 0.f) {
                     if (DET) {  // integer adds commute: order-independent sums (a is already in fixed-point units)
                         // (a per-view record takes at most T flushes, a per-scene one (q = 5..8) V * T: with |a|
                         // below the record's bound no sum reaches 2^62 whatever the flushes' signs; the design value
                         // is |a| <= ~2^51 per flush. A flush beyond the bound is counted and k_preproc_bwd then
                         // poisons the call's gradients with NaN instead of returning possibly wrapped sums)
-                        if (!(fabsf(a) <= (q >= 5 + (AA ? 1 : 0) && q < 9 ? det_lim_s : det_lim_v))) atomicAdd(det_sat, 1u);
-                        atomicAdd(reinterpret_cast<unsigned long long *>(accum) + ai,
+                        if (!(fabsf(a) <= (q >= 5 + (AA ? 1 : 0) && q < (SH ? 6 : 9) ? det_lim_s : det_lim_v)))
+                            atomicAdd(det_sat, 1u);
+                        atomicAdd(reinterpret_cast<unsigned long long *>(shq ? d.sh_part : (void *)accum) + ai,
                                   (unsigned long long)__float2ll_rn(fminf(fmaxf(a, -9.0e18f), 9.0e18f)));
                     } else {
-                        atomicAdd(accum + ai, a);
+                        atomicAdd((shq ? reinterpret_cast<float *>(d.sh_part) : accum) + ai, a);
                     }
                 }
             }
@@ -1516,8 +1515,15 @@ __global__ __launch_bounds__(256) void k_preproc_bwd(Dims d, const float *__rest
 int launch_render_fwd(const Dims &d, const float *gaussians, const float *bg, float *image, float *depth,
                       float *alpha, const Workspace &w, const Layout &L, hipStream_t st) {
     const bool small = d.BV * d.T <= FWD_SMALL_TILES;
-    auto fwd = (d.options & LGM_RENDER_FUSED_LOSS) ? (small ? k_render_fwd<true, 8> : k_render_fwd<true, FWD_FU>)
-                                                   : (small ? k_render_fwd<false, 8> : k_render_fwd<false, FWD_FU>);
+    const bool sh = d.sh_col != nullptr;  // LGM_RENDER_SH_MASK: the colours are staged from the per-view buffer
+    auto pick = [&](auto sh_tag) {
+        constexpr bool SH = decltype(sh_tag)::value;
+        return (d.options & LGM_RENDER_FUSED_LOSS)
+                   ? (small ? k_render_fwd<true, 8, SH> : k_render_fwd<true, FWD_FU, SH>)
+                   : (small ? k_render_fwd<false, 8, SH> : k_render_fwd<false, FWD_FU, SH>);
+    };
+    auto fwd = sh ? pick(std::true_type{}) : pick(std::false_type{});
+    if (sh) gaussians = d.sh_col;
     LGM_LAUNCH("k_render_fwd", st, (fwd<<<(unsigned)(d.BV * d.T), 256, 0, st>>>(
                                        d, L.slot ? (long long)d.N : -1LL, w.tile_start, w.tile_count, w.pairs, w.gP,
                                        w.gQ, gaussians, bg, image, depth, alpha, w.final_T, w.n_contrib, w.wlast,
@@ -1544,6 +1550,11 @@ int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_vi
         set_error("hipMemsetAsync failed");
         return LGM_E_HIP;
     }
+    if ((d.options & LGM_RENDER_BACKWARD_AGAIN) && L.acc.sh_part.bytes &&  // (SH) the per-view colour partials too
+        hipMemsetAsync(w.accum_range(L.acc.sh_part), 0, L.acc.sh_part.bytes, st) != hipSuccess) {
+        set_error("hipMemsetAsync failed");
+        return LGM_E_HIP;
+    }
     const bool loss = (d.options & LGM_RENDER_FUSED_LOSS) != 0, det = (d.options & LGM_RENDER_DETERMINISTIC) != 0;
     if (det) {  // the call's fixed-point scale: max |dL/dpixel| over every seed (k_det_seed_max)
         if (hipMemsetAsync(w.detmax, 0, DET_SLOTS * 4, st) != hipSuccess) {
@@ -1557,21 +1568,24 @@ int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_vi
                                              w.det_sat)));
     }
     const bool aa = (d.options & LGM_RENDER_ANTIALIAS) != 0;
-    auto pick = [&](auto depth_tag) {
-        constexpr bool DP = decltype(depth_tag)::value;
+    const bool sh = d.sh_col != nullptr;  // LGM_RENDER_SH_MASK
+    auto pick = [&](auto depth_tag, auto sh_tag) {
+        constexpr bool DP = decltype(depth_tag)::value, SH = decltype(sh_tag)::value;
         if (aa)
-            return loss ? (det ? k_render_bwd<DP, true, true, true> : k_render_bwd<DP, true, false, true>)
-                        : (det ? k_render_bwd<DP, false, true, true> : k_render_bwd<DP, false, false, true>);
-        return loss ? (det ? k_render_bwd<DP, true, true> : k_render_bwd<DP, true, false>)
-                    : (det ? k_render_bwd<DP, false, true> : k_render_bwd<DP, false, false>);
+            return loss ? (det ? k_render_bwd<DP, true, true, true, SH> : k_render_bwd<DP, true, false, true, SH>)
+                        : (det ? k_render_bwd<DP, false, true, true, SH> : k_render_bwd<DP, false, false, true, SH>);
+        return loss ? (det ? k_render_bwd<DP, true, true, false, SH> : k_render_bwd<DP, true, false, false, SH>)
+                    : (det ? k_render_bwd<DP, false, true, false, SH> : k_render_bwd<DP, false, false, false, SH>);
     };
-    auto bwd = d_depth ? pick(std::true_type{}) : pick(std::false_type{});
+    auto bwd = sh ? (d_depth ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
+                  : (d_depth ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{}));
     // work items: chunk 0 of every tile, then one per checkpoint slot (unused slots exit at once)
     const int M = d.BV * d.T, Mp = round8(M);
     LGM_LAUNCH("k_render_bwd", st, (bwd<<<(unsigned)(Mp + L.ck_slots), 256, 0, st>>>(
                                        d, L.slot ? (long long)d.N : -1LL, w.tile_start, w.tile_count, w.pairs, w.gP,
-                                       w.gQ, gaussians, bg, w.final_T, w.n_contrib, w.wlast, w.cfin, w.ck, w.cklist,
-                                       w.nck, w.ck_counters, L.ck_region, d_image, d_depth, d_alpha, w.cmask, w.accum,
+                                       w.gQ, sh ? d.sh_col : gaussians, bg, w.final_T, w.n_contrib, w.wlast, w.cfin,
+                                       w.ck, w.cklist, w.nck, w.ck_counters, L.ck_region, d_image, d_depth, d_alpha,
+                                       w.cmask, w.accum,
                                        w.detmax, w.det_sat, (long long)cnt_item0(d.BV, d.T, d.N))));
     dim3 grid((d.N + 255) / 256, d.B);
     auto pre = aa ? (d.V <= PRE_MAXV ? k_preproc_bwd<true, true> : k_preproc_bwd<false, true>)

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import sh as shm
 from ._native import ptr
 from .ply import read_ply, write_ply
 
@@ -46,13 +47,22 @@ def _tiles(H: int, W: int) -> int:
 
 
 def _count_pairs(g, cam_view, cam_view_proj, tanx, tany, scale_modifier, H, W):
-    """lgm_render_count_pairs -> device int64 [2]: the (binned, reference) pair counts over all B x V views."""
+    """lgm_render_count_pairs -> device int64 [2]: the (binned, reference) pair counts over all B x V views. The entry
+    point takes no options and reads 14-wide rows: SH rows go in as a contiguous copy of their columns 0:14 (only 0:11
+    are read -- colour does not enter the binning)."""
+    g = _rows14(g)
     B, N, V = g.shape[0], g.shape[1], cam_view.shape[1]
     ws, ws_bytes = nat.workspace("lgm_render_workspace_size", g.device, B, V, N, H, W, 1, min_bytes=0)
     k = torch.zeros(2, dtype=torch.int64, device=g.device)
     nat.call("lgm_render_count_pairs", g.device, B, V, N, H, W, ptr(g), ptr(cam_view), ptr(cam_view_proj), tanx, tany,
              scale_modifier, ptr(ws), ws_bytes, ptr(k))
     return k
+
+
+def _rows14(g):
+    """What lgm_render_count_pairs is handed: the rows themselves if 14 wide, else a contiguous [B,N,14] copy of
+    columns 0:14."""
+    return g if g.shape[-1] == 14 else g[..., :14].contiguous()
 
 
 class _RasterizeBatched(torch.autograd.Function):
@@ -138,14 +148,21 @@ def deterministic_enabled() -> bool:
 
 
 def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, scale_modifier=1.0, clamp=False,
-              gt_images=None, gt_masks=None, deterministic=None, no_cull=False, antialias=False):
+              gt_images=None, gt_masks=None, deterministic=None, no_cull=False, antialias=False, sh_degree=None):
     """Functional form: returns (image [B,V,3,H,W], depth [B,V,1,H,W], alpha [B,V,1,H,W]). The image is
     unclamped unless clamp=True, which applies core/gs.py:87's clamp(0, 1) (and its gradient) inside the kernels.
     With gt_images [B,V,3,H,W] and gt_masks [B,V,1,H,W] a 4th output (loss_mse, mse_image, mse_alpha, psnr) holds
     LGM's training MSE terms (core/models.py:145-148,167), fused into the kernels; it is differentiable.
     no_cull=True bins upstream's full 3-sigma tile rects (LGM_RENDER_NO_CULL: same outputs, more work).
     antialias=True compensates the opacity for the 0.3 px^2 dilation (LGM_RENDER_ANTIALIAS, include/lgm_render.h:
-    o sqrt(det cov / det(cov + 0.3 I)), the 3DGS rasteriser's `antialiasing`), forward and backward."""
+    o sqrt(det cov / det(cov + 0.3 I)), the 3DGS rasteriser's `antialiasing`), forward and backward.
+    sh_degree: view-dependent colour from spherical harmonics (LGM_RENDER_SH_MASK). None infers the degree from the
+    row width: 14 is plain RGB, 23 / 38 / 59 are [B,N,11 + 3K] rows of degree 1 / 2 / 3 (coefficient k of channel c at
+    column 11 + 3k + c, lgm_amd/sh.py); any other width, or one that contradicts an explicit degree, is a ValueError.
+    The camera positions are derived from cam_view."""
+    if gaussians.dim() != 3:
+        raise ValueError(f"gaussians must be [B,N,14] or SH rows [B,N,23 / 38 / 59], got {tuple(gaussians.shape)}")
+    degree = shm.degree_of(gaussians.shape[-1], sh_degree)
     if not gaussians.is_cuda:  # CPU tensors: the torch path of BASELINE config 1 (lgm_amd/cpu.py), never the oracle
         from .cpu import render_cpu
         bgc = torch.as_tensor(bg, dtype=torch.float32).detach().cpu()
@@ -163,8 +180,6 @@ def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, sc
     cv = cam_view.to(dev, torch.float32).contiguous()
     cvp = cam_view_proj.to(dev, torch.float32).contiguous()
     bgt = torch.as_tensor(bg, dtype=torch.float32).to(dev).contiguous().detach()
-    if g.dim() != 3 or g.shape[-1] != 14:
-        raise ValueError(f"gaussians must be [B,N,14], got {tuple(g.shape)}")
     if cv.shape[:2] != cvp.shape[:2] or cv.shape[0] != g.shape[0] or cv.shape[-2:] != (4, 4):
         raise ValueError("cam_view / cam_view_proj must be [B,V,4,4] with B matching gaussians")
     gti = gtm = None
@@ -175,7 +190,7 @@ def rasterize(gaussians, cam_view, cam_view_proj, bg, tanfovx, tanfovy, H, W, sc
         if tuple(gti.shape) != (B, V, 3, H, W) or tuple(gtm.shape) != (B, V, 1, H, W):
             raise ValueError("gt_images / gt_masks must be [B,V,3,H,W] / [B,V,1,H,W]")
     options = (nat.RENDER_CLAMP_IMAGE if clamp else 0) | (nat.RENDER_NO_CULL if no_cull else 0) | \
-        (nat.RENDER_ANTIALIAS if antialias else 0)
+        (nat.RENDER_ANTIALIAS if antialias else 0) | (degree << nat.RENDER_SH_SHIFT)
     if deterministic_enabled() if deterministic is None else deterministic:
         options |= nat.RENDER_DETERMINISTIC
     out = _RasterizeBatched.apply(g, cv, cvp, bgt, float(tanfovx), float(tanfovy), float(scale_modifier),
@@ -194,15 +209,17 @@ def count_pairs(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, scal
 
 
 def forward_state(gaussians, cam_view, cam_view_proj, tanfovx, tanfovy, H, W, scale_modifier=1.0, lists=False,
-                  no_cull=False, records=False, antialias=False):
+                  no_cull=False, records=False, antialias=False, sh_degree=None):
     """Runs one forward and returns what it left in its workspace (numpy, one host sync), for parity tests and
     debugging -- the equivalent of reading upstream's saved buffers (radii, point_list/ranges, n_contrib):
       radii [B,V,N] int32; K_binned / K_reference (as count_pairs); tile_counts [B,V,T] int32;
       n_contrib, final_T [B,V,H,W]; with lists=True, ids[b][v] = the view's tile lists concatenated (tile-major,
       each in compositing order); with records=True, the compositing records P, Q [B,V,N,4] and rects [B,V,N,2]
       (uint32) of lgm_render_records. no_cull=True bins upstream's full 3-sigma rects (LGM_RENDER_NO_CULL);
-      antialias=True renders with LGM_RENDER_ANTIALIAS (the records' L is then log2 of the compensated opacity)."""
-    options = (nat.RENDER_NO_CULL if no_cull else 0) | (nat.RENDER_ANTIALIAS if antialias else 0)
+      antialias=True renders with LGM_RENDER_ANTIALIAS (the records' L is then log2 of the compensated opacity);
+      sh_degree as rasterize (SH rows; the state read here does not depend on the colours)."""
+    options = (nat.RENDER_NO_CULL if no_cull else 0) | (nat.RENDER_ANTIALIAS if antialias else 0) | \
+        (shm.degree_of(gaussians.shape[-1], sh_degree) << nat.RENDER_SH_SHIFT)
     L = nat.lib()
     g = gaussians.float().contiguous()
     dev = g.device
@@ -272,9 +289,10 @@ class GaussianRenderer:
         self.proj_matrix[2, 3] = 1
 
     def render(self, gaussians, cam_view, cam_view_proj, cam_pos, bg_color=None, scale_modifier=1, gt_images=None,
-               gt_masks=None, antialias=None):
-        """core/gs.py:31-98. gaussians [B,N,14]; cam_view, cam_view_proj [B,V,4,4]; cam_pos [B,V,3] (unused without
-        SH, as upstream). Additive: with gt_images / gt_masks (the `images_output` / `masks_output` of
+               gt_masks=None, antialias=None, sh_degree=None):
+        """core/gs.py:31-98. gaussians [B,N,14], or SH rows [B,N,23 / 38 / 59] (sh_degree as rasterize: None infers
+        it from the width); cam_view, cam_view_proj [B,V,4,4]; cam_pos [B,V,3] is accepted and unused: the SH
+        directions take the camera positions the kernels derive from cam_view. Additive: with gt_images / gt_masks (the `images_output` / `masks_output` of
         core/models.py:140-141) the result also holds LGM's MSE loss terms, computed in the render kernels:
         "loss_mse" (differentiable: its backward seeds the render backward in-kernel), "mse_image", "mse_alpha"
         and "psnr" (core/models.py:145-148,165-167). antialias (additive; None reads opt.antialias, default off):
@@ -285,7 +303,8 @@ class GaussianRenderer:
         # core/gs.py:87's clamp(0, 1) and its gradient are applied inside the kernels
         out = rasterize(gaussians, cam_view, cam_view_proj, bg, tan, tan, S, S, scale_modifier, clamp=True,
                         gt_images=gt_images, gt_masks=gt_masks,
-                        antialias=bool(getattr(self.opt, "antialias", False) if antialias is None else antialias))
+                        antialias=bool(getattr(self.opt, "antialias", False) if antialias is None else antialias),
+                        sh_degree=sh_degree)
         res = {"image": out[0], "alpha": out[2], "depth": out[1]}
         if len(out) == 4:
             loss4 = out[3]
@@ -293,22 +312,29 @@ class GaussianRenderer:
         return res
 
     def save_ply(self, gaussians, path, compatible=True):
-        """core/gs.py:101-152: B == 1, prune opacity < 0.005, optionally invert activations (3DGS PLY layout)."""
+        """core/gs.py:101-152: B == 1, prune opacity < 0.005, optionally invert activations (3DGS PLY layout).
+        SH rows [1,N,11 + 3K] (lgm_amd/sh.py) also write f_rest_0 .. f_rest_{3(K-1)-1} in 3DGS's property order
+        (channel-major: f_rest_i holds coefficient 1 + i % (K - 1) of channel i // (K - 1), after f_dc_*); their
+        coefficients are stored as they are (the DC is a coefficient already: no C0 x + 1/2 to invert)."""
         assert gaussians.shape[0] == 1, "only support batch size 1"
         g = gaussians[0].detach().float().cpu()
+        degree = shm.degree_of(g.shape[-1])
         means3D, opacity, scales, rotations = g[:, 0:3], g[:, 3:4], g[:, 4:7], g[:, 7:11]
-        shs = g[:, 11:].unsqueeze(1)
+        shs = g[:, 11:].reshape(g.shape[0], -1, 3)  # [N, K, 3] (K = 1: the RGB)
         mask = opacity.squeeze(-1) >= 0.005
         means3D, opacity, scales, rotations, shs = means3D[mask], opacity[mask], scales[mask], rotations[mask], shs[mask]
         if compatible:
             o = opacity.clamp(1e-6, 1 - 1e-6)
             opacity = torch.log(o / (1 - o))  # kiui.op.inverse_sigmoid
             scales = torch.log(scales + 1e-8)
-            shs = (shs - 0.5) / 0.28209479177387814
-        f_dc = shs.transpose(1, 2).flatten(start_dim=1).contiguous()
-        names = ["x", "y", "z"] + [f"f_dc_{i}" for i in range(f_dc.shape[1])] + ["opacity"] + \
+            if not degree:
+                shs = (shs - 0.5) / 0.28209479177387814
+        f_dc = shs[:, :1].transpose(1, 2).flatten(start_dim=1).contiguous()
+        f_rest = shs[:, 1:].transpose(1, 2).flatten(start_dim=1).contiguous()  # [N, 3 (K - 1)], channel-major
+        names = ["x", "y", "z"] + [f"f_dc_{i}" for i in range(f_dc.shape[1])] + \
+                [f"f_rest_{i}" for i in range(f_rest.shape[1])] + ["opacity"] + \
                 [f"scale_{i}" for i in range(scales.shape[1])] + [f"rot_{i}" for i in range(rotations.shape[1])]
-        data = torch.cat([means3D, f_dc, opacity, scales, rotations], dim=1).numpy().astype(np.float32)
+        data = torch.cat([means3D, f_dc, f_rest, opacity, scales, rotations], dim=1).numpy().astype(np.float32)
         write_ply(path, names, data)
 
     def save_mesh(self, gaussians, path, **kw):
@@ -327,8 +353,12 @@ class GaussianRenderer:
             mesh.save_obj(path)
         return mesh
 
-    def load_ply(self, path, compatible=True):
-        """core/gs.py:154-190: returns a CPU [N,14] tensor."""
+    def load_ply(self, path, compatible=True, sh=False):
+        """core/gs.py:154-190: returns a CPU [N,14] tensor (the f_rest_* properties of an SH file are dropped: its DC
+        colour). sh=True keeps them: a file with 9 / 24 / 45 f_rest_* properties (degree 1 / 2 / 3; another count is
+        a ValueError) gives [N,11 + 3K] SH rows (lgm_amd/sh.py) -- the DC kept as a coefficient, without the
+        C0 x + 1/2 activation, f_rest_i read in 3DGS's channel-major order i = c (K - 1) + (k - 1); a file without
+        f_rest_* gives the [N,14] tensor either way."""
         props = read_ply(path)
         xyz = np.stack([props["x"], props["y"], props["z"]], axis=1)
         print("Number of points at loading : ", xyz.shape[0])
@@ -338,11 +368,19 @@ class GaussianRenderer:
         rn = sorted([k for k in props if k.startswith("rot_")], key=lambda s: int(s.split("_")[-1]))
         scales = np.stack([props[k] for k in sn], axis=1)
         rots = np.stack([props[k] for k in rn], axis=1)
+        rest = sorted([k for k in props if k.startswith("f_rest_")], key=lambda s: int(s.split("_")[-1]))
+        if sh and rest:
+            if len(rest) not in (9, 24, 45):
+                raise ValueError(f"{path}: {len(rest)} f_rest_* properties; SH degree 1 / 2 / 3 has 9 / 24 / 45")
+            K1 = len(rest) // 3  # K - 1; f_rest is [3, K - 1] channel-major -> rows [K - 1, 3]
+            fr = np.stack([props[k] for k in rest], axis=1).reshape(-1, 3, K1).transpose(0, 2, 1).reshape(-1, 3 * K1)
+            shs = np.concatenate([shs, fr], axis=1)
         gaussians = torch.from_numpy(np.concatenate([xyz, opac, scales, rots, shs], axis=1).astype(np.float64)).float()
         if compatible:
             gaussians[..., 3:4] = torch.sigmoid(gaussians[..., 3:4])
             gaussians[..., 4:7] = torch.exp(gaussians[..., 4:7])
-            gaussians[..., 11:] = 0.28209479177387814 * gaussians[..., 11:] + 0.5
+            if gaussians.shape[-1] == 14:
+                gaussians[..., 11:] = 0.28209479177387814 * gaussians[..., 11:] + 0.5
         return gaussians
 
 
