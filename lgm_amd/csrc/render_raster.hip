@@ -108,16 +108,19 @@ __device__ __forceinline__ void stage_dma(Buf &B, int w, unsigned gid, size_t gb
     else lds_dma<12>(gauss + ((size_t)b * N + gid) * 14 + 11, base + (unsigned)offsetof(Buf, R));
 }
 
-// Entry j of a landed chunk: its quadrant mask (the alpha >= 1/255 ellipse against the four 8x8 quadrants) and,
-// for the backward's gradient flush, its Gaussian id.
+// Entry j of a landed chunk: its quadrant mask (the alpha >= 1/255 ellipse against the four 8x8 quadrants), which
+// is also returned (k_render_fwd keeps it for the backward).
+// The reciprocals are v_rcp_f32 (1 ulp): they only place the 1-D minimiser on a rectangle edge, and the minimum
+// found is compared with a threshold inflated by 1e-3 relative (tau, render_common.h), orders of magnitude more
+// than a 1-ulp shift of the minimiser moves a quadratic at its minimum.
 template <class Stage>
-__device__ __forceinline__ void stage_commit(Stage &S, typename Stage::Buf &B, int j, bool have, unsigned gid, int tx0, int ty0,
-                                             bool store_id) {
+__device__ __forceinline__ unsigned char stage_commit(Stage &S, typename Stage::Buf &B, int j, bool have, int tx0,
+                                                      int ty0) {
     unsigned char mask = 0;
     if (have) {
         const float4 p = B.P[j], q = B.Q[j];
-        if (store_id) reinterpret_cast<unsigned *>(&B.R[j])[3] = gid;
-        const float A = -p.z, Bc = -0.5f * p.w, C = -q.x, iA = 1.0f / A, iC = 1.0f / C;  // KQ-scaled (render_common.h)
+        const float A = -p.z, Bc = -0.5f * p.w, C = -q.x;  // KQ-scaled (render_common.h)
+        const float iA = __builtin_amdgcn_rcpf(A), iC = __builtin_amdgcn_rcpf(C);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const float qx = (float)(tx0 + ((k & 1) << 3)), qy = (float)(ty0 + ((k >> 1) << 3));
@@ -126,6 +129,7 @@ __device__ __forceinline__ void stage_commit(Stage &S, typename Stage::Buf &B, i
         }
     }
     S.mask[j] = mask;
+    return mask;
 }
 
 template <class Stage>
@@ -186,7 +190,7 @@ template <bool LOSS, int FU, bool SH = false>  // LOSS: LGM_RENDER_FUSED_LOSS co
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_FU ? 7 : 2))) void k_render_fwd(Dims d, long long slot_stride,
                                                     const int *__restrict__ tile_start,
                                                     const int *__restrict__ tile_count,
-                                                    const unsigned long long *__restrict__ pairs,
+                                                    unsigned long long *__restrict__ pairs,
                                                     const float4 *__restrict__ gP, const float4 *__restrict__ gQ,
                                                     const float *__restrict__ gauss,
                                                     const float *__restrict__ bg, float *__restrict__ out_img,
@@ -213,6 +217,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_F
     int n;
     tile_range(tile, slot_stride, tile_start, tile_count, base, n);
     const unsigned *ids = reinterpret_cast<const unsigned *>(pairs + base);
+    // The quadrant masks of every chunk staged here are kept for k_render_bwd, one byte per list position, in the dead
+    // half of the tile's own pair range: k_sort leaves the n sorted ids as u32 in the first 4 n of its 8 n bytes (every
+    // path: msd_sort's ids_out, the LSD passes' and sort_oversized's in-place ids, a single id in the low half of
+    // its key; slot and packed ranges alike) and nothing reads the rest again. Position p's mask is byte 4 n + p.
+    unsigned char *qmask = reinterpret_cast<unsigned char *>(pairs + base) + 4 * (size_t)n;
     const size_t gbase = (size_t)bv * d.N;
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     init_sentinel(S);
@@ -248,8 +257,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FU == FWD_F
         StageBuf &B = S.buf[0];
         if (k < n) stage_dma<SH>(B, w, id_a, gbase, b, d.N, gP, gQ, gauss);
         vm_wait();
-        stage_commit(S, B, tid, k < n, 0u, tx0, ty0, false);
+        const unsigned char qm = stage_commit(S, B, tid, k < n, tx0, ty0);
         __syncthreads();
+        if (k < n) qmask[k] = qm;  // (one coalesced 256-B store per chunk; drains during the compositing)
 #ifdef LGM_FWD_STAMPS
         const unsigned long long fs_b = sec_stamp();
         fs_head += fs_b - fs_a;
@@ -714,7 +724,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
     __shared__ __attribute__((aligned(16))) float sWU[4][16 * WU_LD];  // read as float4: keep 16-B aligned
     // the chunk's gradient partials (rows q * LS + j; a needle's conic partials in rows NV .. NV + 2 for the fp64
     // flush) and its Gaussian ids, written by the conversion and read by the flush. Their own buffer (not a dead WU
-    // image) lets a wave start the next chunk's quadrant tests and entries right after its share of the flush, while
+    // image) lets a wave start the next chunk's compaction and entries right after its share of the flush, while
     // other waves still flush: one barrier less per chunk
     __shared__ __attribute__((aligned(16))) float sO[(NV + 3) * LS];
     __shared__ unsigned sId[CH];
@@ -796,9 +806,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
         vm_wait();
         return;
     }
+    // Quadrant masks from the forward (k_render_fwd's qmask: byte 4 n + p of the tile's pair range for list position
+    // p), one chunk ahead in a register like the ids. Only positions < min(s1, wlast) are loaded: all of them lie in
+    // chunks the forward staged (wlast is a position it composited), so every byte read was written by this forward.
+    // Why the forward's verdict serves: a pixel took a contribution only from an entry the forward listed for the
+    // pixel's quadrant, so the masks cover every (entry, quadrant) with a non-zero gradient; an entry a wave does
+    // not list adds exact zeros (its moment slot stays zeroed), and each listed entry's moments sit in an MFMA column
+    // of their own, whatever else shares the batch. The float-mode gradients therefore keep their values up to the
+    // order of the atomics, and the deterministic ones are bitwise those of the backward's own retest.
+    const unsigned char *qmask = reinterpret_cast<const unsigned char *>(pairs + base) + 4 * (size_t)n;
+    const int qend = min(s1, wlast);  // (per wave)
+    unsigned qm = s0 + lane < qend ? qmask[(unsigned)(s0 + lane)] : 0u;
     const unsigned long long t_item = d.counters ? __builtin_amdgcn_s_memrealtime() : 0ull;
 #ifdef LGM_BWD_STAMPS  // section cycles of this wave (diagnostic build; counters [0..7], scripts/diag_bwd_stamps.py)
-    // [0] prologue, [1] chunk-top barrier, [2] chunk head (quadrant tests, compaction, next DMA issue), [3] entries
+    // [0] prologue, [1] the lane's quadrant verdict, [2] rest of the chunk head (compaction, next DMA issue), [3] entries
     // loop, [4] the post-entries barrier + moments -> partials, [5] the DMA wait (vmcnt 0), [6] the pre-flush
     // barrier, [7] the gradient atomics
     unsigned long long sec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -932,7 +953,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
     // so no staging load queues behind them; the sorted ids run one chunk further ahead in a register.
     // Two barriers per chunk: P (after the entries loop: every wave's moments are in its slot) and F (before the
     // flush: the partials are in sO, and the stager's next chunk has landed). The chunk-top barrier of rounds 1-5 is
-    // gone: a wave goes from its share of chunk c's flush straight into chunk c + 1's quadrant tests and entries
+    // gone: a wave goes from its share of chunk c's flush straight into chunk c + 1's compaction and entries
     // while the others still flush. That is safe because nothing the flush reads is written before the next P:
     // the partials and ids live in sO / sId (rewritten only by the next conversion, after P), the needle flag has one
     // word per chunk parity, and the next chunk's DMA overwrites the buffer of chunk c - 1, whose last reader (the
@@ -950,24 +971,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
         SEC_T(ts_c0b);
 #endif
         auto &B = S.buf[cur];
-        // one row per lane: every wave tests all CH entries against its OWN quadrant (one ellipse test per lane
-        // instead of four per staging thread) and the ballot is its compaction mask (no shared mask, no barrier)
+        // one row per lane: every wave takes its OWN quadrant's bit of the forward's mask for each of the CH entries
+        // (qm, loaded a chunk ahead) and the ballot is its compaction mask (no shared mask, no barrier, and neither the
+        // rows' LDS reads, the two IEEE divisions nor the ellipse test the retest cost at the top of every chunk)
         if (stager) reinterpret_cast<unsigned *>(&B.R[lane])[3] = id_cur;  // for the gradient flush
         if (!DET && tid == 0) s_ndl[ci & 1] = 0;  // (published by P; the flush of chunk ci - 2 read it before P of ci - 1)
         {  // every wave zeroes its own slot (an entry it skips, or never lists, adds nothing): wave-private, so the
-           // entries loop follows the quadrant tests without a barrier (with the conversion over three waves below:
+           // entries loop follows the compaction without a barrier (with the conversion over three waves below:
            // pool k_render_bwd 642 -> 635 us, bitwise equal, profiles/r04/ab_bwd_conv)
             float4 *z = reinterpret_cast<float4 *>(myAcc);
             for (int q = lane; q < ZSLOT / 4; q += 64) z[q] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         int cnt;
+#ifdef LGM_BWD_STAMPS
+        unsigned long long sec1_chunk = 0;
+#endif
         {
-            bool hit = false;
-            if (b0 + lane < s1 && lane < wlast - b0) {  // positions < wlast only
-                const float4 p = B.P[lane], q = B.Q[lane];
-                const float qx = (float)(tx0 + ((w & 1) << 3)), qy = (float)(ty0 + ((w >> 1) << 3));
-                hit = rec_hits_rect(p, q, qx, qx + 7.0f, qy, qy + 7.0f);
-            }
+#ifdef LGM_BWD_STAMPS
+            SEC_T(ts_c0p);
+#endif
+            bool hit = (qm >> w) & 1u;  // (0 beyond min(s1, wlast): never loaded)
+            qm = b0 + CH + lane < qend ? qmask[(unsigned)(b0 + CH + lane)] : 0u;  // the next chunk's
+#ifdef LGM_BWD_STAMPS
+            int hit_v = hit;
+            asm volatile("" : "+v"(hit_v));  // (the lane's verdict exists before the stamp)
+            hit = hit_v != 0;
+            SEC_T(ts_c0q);
+            sec1_chunk = ts_c0q - ts_c0p;
+            sec[1] += sec1_chunk;  // the lane's quadrant verdict alone ([2] keeps the rest of the head)
+#endif
             const unsigned long long bal = __ballot(hit);
             if (hit) S.list[w][__popcll(bal & lanemask_lt(lane))] = (unsigned short)lane;
             cnt = __popcll(bal);
@@ -980,7 +1012,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH ? 2 :
         static_assert(MB == 8, "one batch = two 4-entry list words");
 #ifdef LGM_BWD_STAMPS
         SEC_T(ts_c1);
-        SEC_ADD(sec[2], ts_c0b, ts_c1);  // chunk head: quadrant tests + compaction, next DMA issue ([1]: unused)
+        SEC_ADD(sec[2], ts_c0b, ts_c1);  // chunk head: slot zeroing, compaction, next DMA issue ...
+        sec[2] -= sec1_chunk;            // ... without the quadrant verdict, which [1] holds
 #endif
         const int lastrel = last - b0;  // this pixel's last contributor, relative to the chunk
         uint2 lraw[2];  // the next step's list words, read one step ahead

@@ -29,7 +29,7 @@ for it in range(6):
         torch.cuda.synchronize()
     g.grad = None
 c = cnt[:8].tolist()
-names = ["prologue", "top_barrier", "chunk_head", "entries", "barrier_partials", "dma_wait", "flush_barrier",
+names = ["prologue", "quadrant_verdict", "chunk_head_rest", "entries", "barrier_partials", "dma_wait", "flush_barrier",
          "atomics"]
 tot = sum(c)
 res = {n: {"Gcyc": round(v / 1e9, 3), "share": round(v / max(tot, 1), 3)} for n, v in zip(names, c)}
