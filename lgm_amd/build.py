@@ -8,8 +8,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCES = ["csrc/common.hip", "csrc/render_bin.hip", "csrc/render_raster.hip", "csrc/render_sh.hip",
-           "csrc/render_api.hip",
+SOURCES = ["csrc/common.hip", "csrc/render_bin.hip", "csrc/render_fwd.hip", "csrc/render_bwd.hip",
+           "csrc/render_preproc_bwd.hip", "csrc/render_sh.hip", "csrc/render_api.hip",
            "csrc/attention.hip", "csrc/head.hip", "csrc/mvattn.hip", "csrc/wgrad.hip", "csrc/gnsilu.hip",
            "csrc/lpips.hip", "csrc/data.hip", "csrc/optim.hip", "csrc/conv_wgrad.hip",
            "csrc/conv_fwd.hip", "csrc/mesh.hip", "csrc/meshraster.hip"]
@@ -26,13 +26,18 @@ def sources():
     return [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
 
 
-def needs_build() -> bool:
-    if not os.path.exists(OUT):
-        return True
-    t = os.path.getmtime(OUT)
-    deps = sources() + [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))] + \
+def headers():
+    return [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))] + \
         [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith(".h")]
-    return any(os.path.getmtime(p) > t for p in deps)
+
+
+def newer(deps, target) -> bool:
+    """Is `target` missing, or any of `deps` newer than it?"""
+    return not os.path.exists(target) or any(os.path.getmtime(p) > os.path.getmtime(target) for p in deps)
+
+
+def needs_build() -> bool:
+    return newer(sources() + headers(), OUT)
 
 
 def compile_cmd(src: str, obj: str, defines=()) -> list:
@@ -46,23 +51,26 @@ def compile_cmd(src: str, obj: str, defines=()) -> list:
 
 
 def build(force: bool = False, verbose: bool = False, out: str = None, defines=()) -> str:
-    """Compile every source and link the shared library (`out` and `defines` build A/B variants)."""
+    """Compile the sources and link the shared library (`out` and `defines` build A/B variants, always in full; the
+    default library recompiles only the objects older than their source or any header unless `force`)."""
     out = out or OUT
     if out == OUT and not force and not needs_build():
         return OUT
     os.makedirs(os.path.dirname(out), exist_ok=True)
     objs, cmds = [], []
-    tag = "" if out == OUT else "." + os.path.basename(out)
+    tag = "" if out == OUT and not defines else "." + os.path.basename(out)  # (variants never share the default objects)
     for src in sources():
         obj = os.path.join(HERE, "_lib", os.path.basename(src) + tag + ".o")
+        objs.append(obj)
+        if not tag and not force and not newer([src] + headers(), obj):
+            continue
         cmd = compile_cmd(src, obj, defines)
         if verbose:
             print(" ".join(cmd))
         cmds.append(cmd)
-        objs.append(obj)
     # the sources compile independently: in parallel (at most 8 at once: the container and the GPU box's share)
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(8, len(cmds))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(8, len(cmds)))) as ex:
         for r in list(ex.map(lambda c: subprocess.run(c), cmds)):
             if r.returncode:
                 raise subprocess.CalledProcessError(r.returncode, r.args)

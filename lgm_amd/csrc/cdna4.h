@@ -1,6 +1,6 @@
 // lgm_amd/csrc/cdna4.h -- the gfx950 device idioms that more than one kernel file uses: the 16-bit MFMA, LDS DMA with
-// its counted wait, and the transposing LDS read. Everything is inlined; tile layouts, swizzles and address arithmetic
-// stay with the kernels.
+// its counted wait, the ballot prefix mask and the transposing LDS read. Everything is inlined; tile layouts, swizzles
+// and address arithmetic stay with the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,6 +81,9 @@ template <int N = 0> __device__ __forceinline__ void vm_wait() {
     static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit count");
     __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
 }
+
+// The lanes below `lane` as a ballot mask (a compaction's prefix: __popcll(ballot & lanemask_lt(lane))).
+__device__ __forceinline__ unsigned long long lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
 
 // Two transposing reads (ds_read_b64_tr_b16) joined into one 8-element MFMA operand: p_lo supplies elements 0 .. 3 and
 // p_hi 4 .. 7. The read moves 16-bit elements whatever their type, so the i16 form serves bf16 and f16.

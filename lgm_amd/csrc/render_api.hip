@@ -2,8 +2,8 @@
 //
 // lgm_render_forward  replaces the B*V calls of _C.rasterize_gaussians made by core/gs.py:73-85;
 // lgm_render_backward replaces the B*V calls of _C.rasterize_gaussians_backward plus autograd's sum over views
-// through the slices of core/gs.py:45-49. Kernels: render_bin.hip (preprocess, binning, sort) and
-// render_raster.hip (compositing forward/backward, projection backward).
+// through the slices of core/gs.py:45-49. Kernels: render_bin.hip (preprocess, binning, sort),
+// render_fwd.hip / render_bwd.hip (compositing forward / backward), render_preproc_bwd.hip (projection backward).
 #include "render_common.h"
 
 namespace {

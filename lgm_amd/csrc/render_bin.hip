@@ -13,6 +13,7 @@
 //                      ordered by Gaussian id, which is exactly upstream's order: its LSD sort is stable on
 //                      index-ordered pairs. Buckets > RS_CAP (4032) use an in-place bitonic network on the u64
 //                      composite key (LDS blocks + global merge stages).
+#include "cdna4.h"
 #include "render_common.h"
 
 namespace lgm {
@@ -483,8 +484,6 @@ static_assert(RS_CAP < 65536, "u16 counters");
 static_assert(RS_LDS >= RS_OBLK * 8, "sort_oversized reuses the image as u64[RS_OBLK]");
 static_assert(RS_LDS + 512 <= 160 * 1024 / 4, "4 sort workgroups per CU (with the static __shared__ words)");
 static_assert(RS_B % RS_THREADS == 0 || RS_THREADS % RS_B == 0, "bucket scan layout");
-
-__device__ __forceinline__ unsigned long long lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
 
 // Lanes of the wavefront holding the same nbits-bit digit as this lane (restricted to valid lanes).
 __device__ __forceinline__ unsigned long long match_digit(unsigned dgt, bool valid, int nbits) {

@@ -248,11 +248,6 @@ __device__ __forceinline__ bool rec_needle(float Ap, float Bp, float Cp) {
     const float sac = Ap + Cp, dq = Ap * Cp - 0.25f * Bp * Bp;
     return !(sac * sac <= ACC_NEEDLE * dq);  // (dq <= 0 or NaN: flagged)
 }
-__device__ __forceinline__ bool rec_hits_rect(const float4 &p, const float4 &q, float rx0, float rx1, float ry0,
-                                              float ry1) {
-    const float A = -p.z, B = -0.5f * p.w, C = -q.x;
-    return ellipse_hits_rect(p.x, p.y, A, B, C, 1.0f / A, 1.0f / C, q.z, rx0, rx1, ry0, ry1);
-}
 // the upstream conic and opacity back from a record (the backward's per-entry gradient conversion)
 __device__ __forceinline__ void rec_conic(const float4 &p, const float4 &q, float &A, float &B, float &C, float &op) {
     A = p.z * (-1.0f / KQ);
@@ -384,7 +379,19 @@ __device__ __forceinline__ void load_gaussian(const float *__restrict__ src, flo
     }
 }
 
-// Deterministic mode's per-call scale (render_raster.hip, "Deterministic mode", explains the units).
+// ---- Deterministic mode (LGM_RENDER_DETERMINISTIC): int64 fixed-point accumulators with scales that follow the
+// data, so neither tiny nor huge gradients lose their meaning.
+//  * a per-call scale 2^s with s = DET_BITS - exponent(max |dL/dpixel| over every seed): the accumulators' unit is
+//    2^-DET_BITS of the largest per-pixel seed, whatever the loss normalisation (LGM's mean-MSE gives dL/dpixel
+//    ~1e-9 at 8 x 8 views of 512^2: a fixed 2^-32 unit would leave its partials only tens of units);
+//  * per (view, Gaussian) power-of-two normalisers of the view-dependent partials, from the compositing record (so
+//    k_render_bwd and k_preproc_bwd derive bitwise the same exponents): dL/dmean2D by (W/2) sqrt(A) (resp. (H/2)
+//    sqrt(C)) and dL/dconic by 1 / Sigma_xx, 1 / sqrt(Sigma_xx Sigma_yy), 1 / Sigma_yy (Sigma = conic^-1): with
+//    alpha >= 1/255 only where q <= 2 ln 255, each normalised per-pixel term is bounded by a small constant times
+//    |dL/dG|, so a large, elongated Gaussian's conic partials (pixel offsets of hundreds) cannot overflow int64 and a
+//    small one's keep their resolution.
+// Every power-of-two scaling is exact, so the only rounding is each flush's conversion to an integer (nearest).
+// (k_render_bwd encodes with these, k_preproc_bwd and the SH backward decode.)
 constexpr int DET_BITS = 30;  // seed max -> 2^30 units: per flush |value| <= ~2^51, sums of 2^11 flushes < 2^63
 __device__ __forceinline__ int f32_exp(float x) { return (int)((__float_as_uint(x) >> 23) & 0xffu) - 127; }
 constexpr int DET_SLOTS = 64;  // k_det_seed_max spreads its atomics over this many words (same-address atomics serialise)
@@ -399,6 +406,33 @@ __device__ __forceinline__ int det_seed_shift(const unsigned *det_max) {  // s: 
     const float m = __uint_as_float(mb);
     return (m > 0.f && m < 3.0e38f) ? DET_BITS - f32_exp(m) : 0;
 }
+
+struct DetNorm {
+    int k[6];  // exponents of the view record's slots: mean2D x, y, conic A, B, C, depth
+};
+__device__ __forceinline__ DetNorm det_norm(float Ap, float Bp, float Cp, int W, int H) {
+#pragma clang fp contract(off)
+    DetNorm n;
+    const float detp = Ap * Cp - 0.25f * (Bp * Bp);  // KQ^2 det(conic): the record holds -KQ A, -2 KQ B, -KQ C
+    if (!(detp > 0.f) || !(detp < 3.0e38f) || !(Ap < 0.f) || !(Cp < 0.f)) {
+        for (int q = 0; q < 6; q++) n.k[q] = 0;
+        return n;
+    }
+    const int ea = f32_exp(-Ap), ec = f32_exp(-Cp), ed = f32_exp(detp);
+    auto cl = [](int x) { return min(60, max(-60, x)); };
+    n.k[0] = cl(-(f32_exp(0.5f * (float)W) + (ea >> 1)));
+    n.k[1] = cl(-(f32_exp(0.5f * (float)H) + (ec >> 1)));
+    n.k[2] = cl(ed - ec);              // 1 / Sigma_xx ~ det / C
+    n.k[3] = cl(ed - ((ea + ec) >> 1));  // 1 / sqrt(Sigma_xx Sigma_yy)
+    n.k[4] = cl(ed - ea);              // 1 / Sigma_yy ~ det / A
+    n.k[5] = 0;
+    return n;
+}
+// LGM_RENDER_ANTIALIAS's per-view opacity partial dL/do^ = (sum_p w) / o^: normalised by o^'s own power of two, from
+// the record's L = log2(o^) (<= 0; so k_render_bwd and k_preproc_bwd derive bitwise the same exponent): the
+// normalised flush is the plain pixel sum of w = G dL/dG, bounded like the other per-view partials, however small
+// the compensated opacity of a sub-pixel splat is.
+__device__ __forceinline__ int det_norm_opacity(float L) { return (int)fminf(0.f, fmaxf(-60.f, floorf(L))); }
 
 // Tile bucket of one (view, tile): base offset into `pairs` and entry count.
 // slot_stride < 0 selects packed mode; slot mode uses stride N (possibly 0: then every bucket is empty).
@@ -424,7 +458,17 @@ __device__ __forceinline__ void tile_pixel(int t, int &lx, int &ly) {
     ly = ((w >> 1) << 3) + (l >> 3);
 }
 
-// ---- host launchers (defined in render_bin.hip / render_raster.hip)
+// Runtime flags as compile-time ones, for a launcher that picks a kernel instantiation: with_flags(f, a, b, ...) calls
+// f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...), a generic lambda that returns the kernel's address.
+template <class F>
+auto with_flags(F f) { return f(); }
+template <class F, class... Rest>
+auto with_flags(F f, bool flag, Rest... rest) {
+    auto bind = [&](auto tag) { return with_flags([&](auto... tags) { return f(tag, tags...); }, rest...); };
+    return flag ? bind(std::true_type{}) : bind(std::false_type{});
+}
+
+// ---- host launchers (render_bin.hip, render_fwd.hip, render_bwd.hip, render_preproc_bwd.hip)
 int launch_binning(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
                    const Workspace &w, const Layout &L, int *radii_out, long long *stats_out, bool count_only,
                    hipStream_t st);
@@ -436,6 +480,9 @@ int launch_loss_reduce(const Dims &d, const Workspace &w, hipStream_t st);
 int launch_render_bwd(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
                       const float *bg, const float *d_image, const float *d_depth, const float *d_alpha,
                       float *d_gaussians, float *d_means2D, const Workspace &w, const Layout &L, hipStream_t st);
+// the per-Gaussian projection backward over the accumulators k_render_bwd filled (launch_render_bwd ends with it)
+int launch_preproc_bwd(const Dims &d, const float *gaussians, const float *cam_view, const float *cam_view_proj,
+                       float *d_gaussians, float *d_means2D, const Workspace &w, hipStream_t st);
 // LGM_RENDER_SH_MASK (render_sh.hip): `wide` / `d_wide` are the caller's [B,N,11+3K] rows. launch_sh_pack runs ahead
 // of the binning (the 14-wide copy, the colour partials' zeroing), launch_sh_colour between the binning and
 // launch_render_fwd, launch_sh_bwd after launch_render_bwd.

@@ -200,7 +200,7 @@ struct Layout {
 };
 
 // options: the call's LGM_RENDER_* bits. Two of them shape the workspace.
-// LGM_RENDER_DETERMINISTIC: the gradient accumulators are int64 fixed point (data-scaled units, see render_raster.hip
+// LGM_RENDER_DETERMINISTIC: the gradient accumulators are int64 fixed point (data-scaled units, see render_common.h
 // det_norm) instead of fp32 -- integer atomics commute, so the backward's sums do not depend on the order of its work
 // items -- and there are no backward checkpoints: one backward work item per tile, so how a tile's walk splits into
 // work items cannot depend on which tiles won the shared pool's slot counters (a racing split changes the backward's

@@ -6,8 +6,8 @@ edit to the kernel would otherwise lose silently:
   - no private segment;
   - at most 40,960 B of static LDS (a quarter of the CU's 160 KiB).
 k_render_fwd<false, 4> (every launch that fills the chip) runs 7 waves per SIMD: at most 72 VGPRs.
-The figures are clang's kernel-resource-usage remarks for render_raster.hip compiled with lgm_amd/build.py's own
-line (as tests/test_bin_resources.py does for k_bin).
+The figures are clang's kernel-resource-usage remarks for render_bwd.hip and render_fwd.hip compiled with
+lgm_amd/build.py's own line (as tests/test_bin_resources.py does for k_bin).
 """
 import os
 import re
@@ -25,16 +25,21 @@ FWD_POOL = "12k_render_fwdILb0ELi4ELb0EE"
 
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
-    """{mangled kernel name: {remark field: int}} of every kernel of render_raster.hip."""
+    """{mangled kernel name: {remark field: int}} of every kernel of render_bwd.hip and render_fwd.hip."""
     if not (os.path.exists(B.HIPCC) or shutil.which(B.HIPCC)):
         pytest.fail(f"no HIP compiler at {B.HIPCC}")
-    src = os.path.join(B.HERE, "csrc", "render_raster.hip")
-    obj = str(tmp_path_factory.mktemp("bwd_resources") / "render_raster.o")
-    cmd = B.compile_cmd(src, obj) + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    tmp = tmp_path_factory.mktemp("bwd_resources")
+    runs = [subprocess.Popen(B.compile_cmd(os.path.join(B.HERE, "csrc", name + ".hip"), str(tmp / (name + ".o"))) +
+                             ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"],
+                             stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+            for name in ("render_bwd", "render_fwd")]
+    remarks = ""
+    for r in runs:  # (the two sources compile side by side)
+        err = r.communicate()[1]
+        assert r.returncode == 0, err[-2000:]
+        remarks += err
     out, cur = {}, None
-    for line in r.stderr.splitlines():
+    for line in remarks.splitlines():
         m = re.search(r"remark: (?:[^ ]+: )?\s*([A-Za-z][^:]*): (\S+)", line)
         if not m:
             continue

@@ -1,4 +1,4 @@
-"""The backward's LDS bank layout (lgm_amd/csrc/render_raster.hip, k_render_bwd), restated on the host: the lane
+"""The backward's LDS bank layout (lgm_amd/csrc/render_bwd.hip, k_render_bwd), restated on the host: the lane
 groups and bank functions of MI355X's LDS instructions (ds_write_b32: banks (a/4) mod 32 in two 32-lane groups;
 ds_read_b128: banks (a/4) mod 64, four non-contiguous 16-lane groups) applied to the kernel's address formulas.
 Checks that (1) a batch's moment stores put the 32 lanes of each group on 32 distinct banks whenever the batch's

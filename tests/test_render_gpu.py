@@ -142,7 +142,7 @@ def test_repeated_backward_retain_graph(cuda):
 
 @pytest.mark.parametrize("V", [2, 6])
 def test_deterministic_saturation_poisons_and_resets(cuda, V):
-    """LGM_RENDER_DETERMINISTIC's overflow guard (render_raster.hip k_render_bwd flush): a flush above its record's
+    """LGM_RENDER_DETERMINISTIC's overflow guard (render_bwd.hip k_render_bwd flush): a flush above its record's
     bound (2^62 / 2^ceil(log2 F), F = T flushes for a per-view record, V * T for a per-scene one:
     lgm_render_det_flush_limit_log2, tests/test_abi.py) is counted and k_preproc_bwd poisons the call's gradients
     with NaN. The lgm_diag test hook lowers the bound to 2^1 to force that path; a retain_graph repeat of the same
@@ -257,7 +257,7 @@ def test_fused_clamp_matches_torch_clamp(cuda):
 
 def test_needle_decision_is_contraction_free(cuda):
     """rec_needle on the GPU (lgm_render_needle_flags: the function the binning's flag and the backward flush's
-    re-derivation both call, render_bin.hip / render_raster.hip) decides every near-threshold record exactly as the
+    re-derivation both call, render_bin.hip / render_bwd.hip) decides every near-threshold record exactly as the
     separately rounded IEEE expression, including those where an FMA contraction would flip it."""
     from lgm_amd import _native
     recs, dec = near_threshold_records()
